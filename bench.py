@@ -13,6 +13,10 @@ Driver contract: `python bench.py --gpus N --steps K --warmup W`; for
 N>1 launched under torch.distributed.run, one rank per GPU over RCCL.
 Rank 0 prints ONE JSON line; `value` is the whole-job aggregate
 updates/sec over all N GPUs.
+
+A plain run sets up, warms up, times K steps and prints the result line;
+`--dump-outputs DIR` also saves what the last timed step produced, and
+`--full` is where any further measurement belongs (none exist today).
 """
 
 import argparse
@@ -41,7 +45,39 @@ def parse_args():
     p.add_argument("--mode", choices=["full", "updates", "acting"],
                    default="full",
                    help="isolation: updates-only / acting-only / both")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed "
+                        "step produced (parameters, loss accumulators, "
+                        "last action) as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements beyond the headline "
+                        "figure (none at present: a plain run already "
+                        "times only the flagship workload)")
     return p.parse_args()
+
+
+# --dump-outputs writes at most this many bytes in all
+_DUMP_BUDGET = 64 * 2 ** 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each array as out_dir/<name>.npy in float32.  If together
+    they exceed the budget, every array is cut down to the same fixed,
+    seeded sample of its elements (identical from run to run)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32)
+              for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > _DUMP_BUDGET:
+        keep = 0.99 * _DUMP_BUDGET / total
+        rng = np.random.default_rng(0)
+        for k, a in arrays.items():
+            a = a.reshape(-1)
+            n = max(1, int(a.size * keep))
+            idx = np.sort(rng.choice(a.size, size=n, replace=False))
+            arrays[k] = a[idx]
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def main():
@@ -195,6 +231,7 @@ def main():
 
     do_act = args.mode in ("full", "acting")
     do_upd = args.mode in ("full", "updates")
+    last = {}  # last action / eager losses, for --dump-outputs
 
     def run_window(n_steps):
         """n_steps env steps then n_steps updates (reference structure)."""
@@ -208,6 +245,7 @@ def main():
                                  float(done))
                     state = env.reset() if done else nstate
                 wstore.flush()
+                last["action"] = a_np
             else:
                 from torch_actor_critic_amd.envs.visual import (
                     MultiObservation)
@@ -231,6 +269,7 @@ def main():
                         buffer.store(state, a_np, float(reward), nstate,
                                      float(done))
                         state = env.reset() if done else nstate
+                last["action"] = a_np
         if not do_upd:
             return
         if graph is not None:
@@ -239,10 +278,11 @@ def main():
         else:
             for _ in range(n_steps):
                 samples = buffer.sample(args.batch_size)
-                sac.update_critic(q_opt, actor, critic, target_critic,
-                                  samples)
-                sac.update_policy(pi_opt, actor, critic, samples)
+                loss_q = sac.update_critic(q_opt, actor, critic,
+                                           target_critic, samples)
+                loss_pi = sac.update_policy(pi_opt, actor, critic, samples)
                 sac.update_targets_fast(critic)
+            last["loss_q"], last["loss_pi"] = loss_q, loss_pi
 
     def sync():
         comm.barrier()
@@ -306,6 +346,22 @@ def main():
                 "mode": args.mode,
             },
         }
+        if args.dump_outputs:
+            def host(x):
+                return x.detach().float().cpu().numpy()
+            outs = {"actor_params": host(pi_opt.fp.flat),
+                    "critic_params": host(q_opt.fp.flat),
+                    "target_critic_params": host(target_flat)}
+            if "action" in last:
+                outs["last_action"] = np.asarray(last["action"])
+            if do_upd and graph is not None:
+                # summed over every update since the engine was built
+                outs["loss_q_acc"] = host(graph.loss_q_acc)
+                outs["loss_pi_acc"] = host(graph.loss_pi_acc)
+            elif "loss_q" in last:
+                outs["loss_q"] = host(last["loss_q"])
+                outs["loss_pi"] = host(last["loss_pi"])
+            dump_outputs(args.dump_outputs, outs)
         print(json.dumps(result))
 
     if world > 1:
