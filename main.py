@@ -56,6 +56,9 @@ def load_session(run_id: str, device: torch.device):
     # crashes on resume when it was logged — fixed here)
     environment = sac_params.pop("environment", None)
     sac_params.pop("buffer_size", None)
+    # evaluation settings come from this invocation's CLI flags
+    for key in ("eval_every", "eval_episodes", "eval_envs"):
+        sac_params.pop(key, None)
     sac_params = {
         k: int(float(v)) if float(v).is_integer() else float(v)
         for k, v in sac_params.items()
@@ -134,6 +137,13 @@ def parse_arguments() -> Namespace:
                         help="Welford online state normalization (wires in "
                              "the reference's dead sac/utils.py normalizer "
                              "— SURVEY.md Q9)")
+    parser.add_argument("--eval-every", type=int, default=0,
+                        help="Deterministic evaluation every N epochs "
+                             "(extension; 0 = off)")
+    parser.add_argument("--eval-episodes", type=int, default=10,
+                        help="Episodes per evaluation")
+    parser.add_argument("--eval-envs", type=int, default=8,
+                        help="Env copies stepped in lockstep per evaluation")
     parser.set_defaults(logging=True, render=False)
     return parser.parse_args()
 
@@ -191,6 +201,9 @@ def main():
             ckpt.log_params(params)
             ckpt.log_params({"environment": args.environment,
                              "buffer_size": args.buffer_size})
+            ckpt.log_params({"eval_every": args.eval_every,
+                             "eval_episodes": args.eval_episodes,
+                             "eval_envs": args.eval_envs})
 
     if args.batch_size is not None:
         params["batch_size"] = args.batch_size
@@ -200,7 +213,11 @@ def main():
         params["steps_per_epoch"] = args.steps_per_epoch
 
     sac = SAC(**params, learn_alpha=args.learn_alpha,
-              reference_pi_loss=args.reference_pi_loss)
+              reference_pi_loss=args.reference_pi_loss,
+              eval_every=args.eval_every, eval_episodes=args.eval_episodes,
+              eval_envs=args.eval_envs)
+    environment = args.environment
+    sac.eval_env_fn = lambda: envs.make(environment)
     resumed_la = getattr(pi_opt, "_resume_log_alpha", None)
     if args.learn_alpha and resumed_la is not None:
         import math

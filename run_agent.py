@@ -60,7 +60,30 @@ def parse_arguments() -> Namespace:
     parser.add_argument("--random", action="store_false",
                         dest="deterministic", help="Stochastic policy")
     parser.add_argument("--device", default=None)
+    parser.add_argument("--parallel", type=int, default=1,
+                        help="Env copies stepped in lockstep (1 = the "
+                             "serial reference loop)")
     return parser.parse_args()
+
+
+def run_agent_parallel(actor, environment: str, episodes: int,
+                       parallel: int, deterministic: bool = True,
+                       render: bool = True, device=None,
+                       max_ep_len: int = 5000):
+    """Roll out episodes on `parallel` lockstep env copies with one batched
+    actor call per step; prints mean/std of return and episode length."""
+    import numpy as np
+
+    from torch_actor_critic_amd.algo.evaluate import evaluate
+    res = evaluate(actor, lambda: envs.make(environment), episodes,
+                   max_ep_len, num_envs=parallel,
+                   deterministic=deterministic, device=device, render=render)
+    print(f"return: mean {res['mean_return']:.3f} "
+          f"std {res['std_return']:.3f} | "
+          f"episode length: mean {res['mean_length']:.1f} "
+          f"std {float(np.std(res['lengths'])):.1f} "
+          f"({episodes} episodes, {min(parallel, episodes)} envs)")
+    return res
 
 
 def main():
@@ -77,6 +100,12 @@ def main():
     actor = ckpt.load_model(str(artifact_path / "actor")).to(device)
     actor.eval()
 
+    if args.parallel > 1:
+        max_ep_len = int(float(sac_params.get("max_ep_len", 5000)))
+        run_agent_parallel(actor, environment, args.episodes, args.parallel,
+                           args.deterministic, args.render, device,
+                           max_ep_len)
+        return
     run_agent(actor, env, args.episodes, args.deterministic, args.render,
               device)
 

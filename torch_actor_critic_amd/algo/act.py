@@ -99,6 +99,127 @@ def make_act_path(actor, obs_dim, act_dim, device, philox_seed: int = 0):
         return ActGraph(actor, obs_dim, act_dim, device)
 
 
+class BatchedActKernel:
+    """Batched acting path for evaluation: the whole MLP-actor forward for
+    up to ``max_rows`` states runs as ONE launch
+    (ops/csrc/fused.hip::act_batch_kernel), deterministic or stochastic.
+
+    Evaluation is not the latency-critical serial path, so I/O goes
+    through device buffers with pinned staging copies and one event sync.
+    The Philox counter is a host-side Python int passed to the kernel by
+    value and bumped only by stochastic calls — nothing here shares state
+    with the training ``ActKernel``."""
+
+    path = "kernel"
+    MAX_LAYERS = 4      # ACT_MAXL
+    MAX_OBS = 512       # ACT_MAXW
+
+    def __init__(self, actor, obs_dim: int, act_dim: int, max_rows: int,
+                 device: torch.device, philox_seed: int = 0):
+        from ..models.mlp import Actor as MlpActor
+        from ..ops import require_extension
+        if type(actor) is not MlpActor:
+            raise TypeError("BatchedActKernel needs the plain MLP Actor")
+        if (any(l.out_features > 256 for l in actor.layers)
+                or not 1 <= len(actor.layers) <= self.MAX_LAYERS
+                or act_dim > 64 or obs_dim > self.MAX_OBS):
+            raise ValueError("shape outside act-kernel limits")
+        if torch.device(device).type != "cuda":
+            raise ValueError("BatchedActKernel needs a cuda device")
+        if max_rows < 1:
+            raise ValueError("max_rows must be >= 1")
+        self.ext = require_extension()
+        self.actor = actor
+        self.obs_dim = int(obs_dim)
+        self.act_dim = int(act_dim)
+        self.max_rows = int(max_rows)
+        self.act_limit = float(actor.act_limit)
+        self.lo = float(actor.log_min_std)
+        self.hi = float(actor.log_max_std)
+        self.seed = philox_seed ^ 0xE7A1
+        self.ctr = 0    # host-side step counter (stochastic calls only)
+        self.obs_in = torch.zeros(max_rows, obs_dim, device=device)
+        self.obs_pin = torch.zeros(max_rows, obs_dim, pin_memory=True)
+        self.act_out = torch.zeros(max_rows, act_dim, device=device)
+        self.act_pin = torch.zeros(max_rows, act_dim, pin_memory=True)
+        self.ev = torch.cuda.Event()
+
+    def launch(self, n: int, deterministic: bool, ctr: int):
+        """One kernel launch on rows [0, n) of obs_in -> act_out with the
+        actor's live weights."""
+        a = self.actor
+        self.ext.act_batch(
+            self.obs_in, [l.weight for l in a.layers],
+            [l.bias for l in a.layers], a.mu_layer.weight, a.mu_layer.bias,
+            a.log_std_layer.weight, a.log_std_layer.bias, self.act_out,
+            n, bool(deterministic), int(ctr), self.seed, self.act_limit,
+            self.lo, self.hi)
+
+    def act(self, states, deterministic: bool = True) -> np.ndarray:
+        s = np.asarray(states, dtype=np.float32).reshape(-1, self.obs_dim)
+        n = s.shape[0]
+        if not 1 <= n <= self.max_rows:
+            raise ValueError(f"{n} states for max_rows={self.max_rows}")
+        self.obs_pin[:n].copy_(torch.from_numpy(s))
+        self.obs_in[:n].copy_(self.obs_pin[:n], non_blocking=True)
+        if not deterministic:
+            self.ctr += 1
+        self.launch(n, deterministic, self.ctr)
+        self.act_pin[:n].copy_(self.act_out[:n], non_blocking=True)
+        self.ev.record()
+        self.ev.synchronize()
+        return self.act_pin[:n].numpy().copy()
+
+
+class EagerBatchedAct:
+    """Fallback with BatchedActKernel's ``act`` signature: vector
+    observations are stacked into one actor call; MultiObservation states
+    go through the actor one env at a time (the visual models treat
+    batched and unbatched inputs differently — DEVIATIONS Q7 — so
+    stacking them is unsafe)."""
+
+    path = "eager"
+
+    def __init__(self, actor, device=None):
+        self.actor = actor
+        self.device = device or next(actor.parameters()).device
+
+    def act(self, states, deterministic: bool = True) -> np.ndarray:
+        from ..envs.visual import MultiObservation
+        with torch.no_grad():
+            if len(states) and isinstance(states[0], MultiObservation):
+                out = []
+                for st in states:
+                    mo = MultiObservation(st.features.to(self.device),
+                                          st.frame.to(self.device))
+                    a, _ = self.actor(mo, deterministic=deterministic,
+                                      with_logprob=False)
+                    out.append(a.detach().cpu().numpy().reshape(-1))
+                return np.stack(out)
+            s = torch.as_tensor(np.asarray(states, dtype=np.float32),
+                                device=self.device)
+            if s.ndim == 1:
+                s = s.unsqueeze(0)
+            a, _ = self.actor(s, deterministic=deterministic,
+                              with_logprob=False)
+        return a.detach().cpu().numpy()
+
+
+def make_batched_act_path(actor, obs_dim, act_dim, max_rows, device,
+                          philox_seed: int = 0):
+    """Batched acting path for evaluation: the one-launch kernel on cuda
+    when the actor fits its limits, the eager path otherwise (CPU, visual
+    actors, oversize MLPs).  ``.path`` is "kernel" or "eager"."""
+    device = torch.device(device)
+    if device.type == "cuda":
+        try:
+            return BatchedActKernel(actor, obs_dim, act_dim, max_rows,
+                                    device, philox_seed)
+        except (TypeError, ValueError):
+            pass
+    return EagerBatchedAct(actor, device)
+
+
 class ActGraph:
     """hipGraph-captured single-state stochastic actor forward."""
 

@@ -113,6 +113,9 @@ class SAC:
         learn_alpha: bool = False,
         target_entropy: t.Optional[float] = None,
         use_graph: bool = True,
+        eval_every: int = 0,
+        eval_episodes: int = 10,
+        eval_envs: int = 8,
     ):
         self.alpha = float(alpha)
         self.gamma = float(gamma)
@@ -147,6 +150,16 @@ class SAC:
         # the same statistics snapshot taken at the top of the env step;
         # the update path then consumes normalized states only.
         self.normalizer = None
+
+        # periodic deterministic evaluation (extension; default off =
+        # reference-faithful): every `eval_every` epochs, `eval_episodes`
+        # episodes on `eval_envs` lockstep env copies built by
+        # `eval_env_fn` (set by the caller, like `normalizer`)
+        self.eval_every = int(eval_every)
+        self.eval_episodes = int(eval_episodes)
+        self.eval_envs = int(eval_envs)
+        self.eval_env_fn: t.Optional[t.Callable[[], t.Any]] = None
+        self._eval_act_path = None
 
     # -- single-module updates (reference method surface) ---------------
 
@@ -303,6 +316,39 @@ class SAC:
             s = self._state_to_device(state, device)
             action, _ = actor(s, deterministic=False, with_logprob=False)
         return action.detach().cpu().numpy()
+
+    def _run_evaluation(self, actor, device):
+        """Deterministic evaluation of the live actor on fresh env copies.
+        Every rank plays ceil(eval_episodes / world) episodes (seeds offset
+        per rank) and the per-episode results are merged with the same
+        collective as the training stats, so ranks stay in step.  Touches
+        neither the training env, the buffer, the training act path nor
+        the normalizer statistics."""
+        from .evaluate import evaluate
+        world = comm.num_procs()
+        n_local = -(-self.eval_episodes // world)
+        if (self._eval_act_path is None
+                or self._eval_act_path.actor is not actor):
+            # built once per actor and reused by every evaluation
+            from .act import make_batched_act_path
+            probe = self.eval_env_fn()
+            self._eval_act_path = make_batched_act_path(
+                actor, probe.observation_space.shape[0],
+                probe.action_space.shape[0], max(self.eval_envs, 1),
+                device, 10000 * comm.proc_id())
+            if hasattr(probe, "close"):
+                probe.close()
+        res = evaluate(
+            actor, self.eval_env_fn, n_local, self.max_ep_len,
+            num_envs=self.eval_envs, deterministic=True, device=device,
+            normalizer=self.normalizer,
+            seed=12345 + 1000 * comm.proc_id(),
+            act_path=self._eval_act_path)
+        rets = comm.gather_stats(res["returns"])
+        lens = comm.gather_stats([float(n) for n in res["lengths"]])
+        return {"eval_reward": float(np.mean(rets)),
+                "eval_reward_std": float(np.std(rets)),
+                "eval_episode_length": float(np.mean(lens))}
 
     # -- main loop --------------------------------------------------------
 
@@ -527,13 +573,22 @@ class SAC:
                     metrics["allreduce_ms_per_call"] = (
                         1000.0 * cs["allreduce_s"] / cs["allreduce_n"])
 
+            # periodic deterministic evaluation (all ranks; its metrics
+            # are per-epoch extras, never carried over in `metrics`)
+            eval_metrics = {}
+            if (self.eval_every > 0 and self.eval_env_fn is not None
+                    and (e + 1) % self.eval_every == 0):
+                eval_metrics = self._run_evaluation(actor, device)
+                thr.reset()   # evaluation time is not training throughput
+
             if rank0 and logging:
                 if (e + 1) % self.save_every == 0:
                     self.save_model(actor, critic, pi_opt, q_opt, e)
-                ckpt.log_metrics(metrics, step=e)
+                ckpt.log_metrics({**metrics, **eval_metrics}, step=e)
             if rank0:
-                pbar.set_postfix(step=step, **{k: round(v, 3)
-                                               for k, v in metrics.items()})
+                pbar.set_postfix(step=step, **{
+                    k: round(v, 3)
+                    for k, v in {**metrics, **eval_metrics}.items()})
 
             # fresh episode each epoch (reference algorithm.py:305-307)
             state = env.reset()

@@ -1367,6 +1367,115 @@ void act_kernel(ActArgs a, ActPinned hp) {
   }
 }
 
+// ---------------------------------------------------------------------------
+// Batched whole-policy action kernel (evaluation path): the actor forward
+// for N states in ONE launch.  Each block owns a tile of ACTB_R rows staged
+// in LDS; each thread owns one output neuron, reads its weight row once and
+// keeps ACTB_R accumulators, so weight traffic is paid once per tile
+// instead of once per row.  Deterministic mode (tanh(mu) * act_limit)
+// draws no noise; stochastic mode keys Philox on a counter passed BY VALUE
+// (several blocks run, so act_kernel's single-block self-bump does not
+// carry over) and a subsequence unique per (row, action index).
+// ---------------------------------------------------------------------------
+
+constexpr int ACTB_R = 8;
+
+__global__ __launch_bounds__(256)
+void act_batch_kernel(ActArgs a, int N, int ldx, int deterministic,
+                      unsigned long long ctr_val) {
+  __shared__ __attribute__((aligned(16))) float buf[2][ACTB_R][ACT_MAXW];
+  const int tid = threadIdx.x;
+  const int row0 = blockIdx.x * ACTB_R;
+  const int nrow = min(ACTB_R, N - row0);
+
+  // rows past N are zero-filled, never read from x
+  for (int i = tid; i < ACTB_R * a.O; i += blockDim.x) {
+    const int r = i / a.O, k = i - r * a.O;
+    buf[0][r][k] = r < nrow ? a.x[(int64_t)(row0 + r) * ldx + k] : 0.f;
+  }
+  __syncthreads();
+
+  int cur = 0, K = a.O;
+  for (int L = 0; L < a.n_layers; ++L) {
+    const int H = a.width[L];
+    float acc[ACTB_R];
+    if (tid < H) {
+      const float bias = a.b[L][tid];
+#pragma unroll
+      for (int r = 0; r < ACTB_R; ++r) acc[r] = bias;
+      const float* wr = a.w[L] + (int64_t)tid * K;
+      int k = 0;
+      for (; k + 4 <= K; k += 4) {
+        const float w0 = wr[k], w1 = wr[k+1], w2 = wr[k+2], w3 = wr[k+3];
+#pragma unroll
+        for (int r = 0; r < ACTB_R; ++r) {
+          const float* h = &buf[cur][r][k];
+          acc[r] += w0 * h[0] + w1 * h[1] + w2 * h[2] + w3 * h[3];
+        }
+      }
+      for (; k < K; ++k) {
+        const float w0 = wr[k];
+#pragma unroll
+        for (int r = 0; r < ACTB_R; ++r) acc[r] += w0 * buf[cur][r][k];
+      }
+#pragma unroll
+      for (int r = 0; r < ACTB_R; ++r)
+        buf[1 - cur][r][tid] = fmaxf(acc[r], 0.f);
+    }
+    __syncthreads();
+    cur ^= 1;
+    K = H;
+  }
+
+  // heads + tanh squash
+  if (tid < a.A) {
+    float mu[ACTB_R], ls[ACTB_R];
+    const float bm = a.bmu[tid];
+    const float* wm = a.wmu + (int64_t)tid * K;
+#pragma unroll
+    for (int r = 0; r < ACTB_R; ++r) mu[r] = bm;
+    if (deterministic) {
+      for (int k = 0; k < K; ++k) {
+        const float w = wm[k];
+#pragma unroll
+        for (int r = 0; r < ACTB_R; ++r) mu[r] += w * buf[cur][r][k];
+      }
+#pragma unroll
+      for (int r = 0; r < ACTB_R; ++r)
+        if (r < nrow)
+          a.action[(int64_t)(row0 + r) * a.A + tid] =
+              tanhf(mu[r]) * a.act_limit;
+    } else {
+      const float bl = a.bls[tid];
+      const float* wl = a.wls + (int64_t)tid * K;
+#pragma unroll
+      for (int r = 0; r < ACTB_R; ++r) ls[r] = bl;
+      for (int k = 0; k < K; ++k) {
+        const float w = wm[k], v = wl[k];
+#pragma unroll
+        for (int r = 0; r < ACTB_R; ++r) {
+          const float h = buf[cur][r][k];
+          mu[r] += w * h;
+          ls[r] += v * h;
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < ACTB_R; ++r) {
+        if (r < nrow) {
+          const float l = fminf(fmaxf(ls[r], a.lo), a.hi);
+          P4 p = philox_(a.seed ^ 0x2545f4914f6cdd1dull, ctr_val,
+                         (uint64_t)(row0 + r) * (uint64_t)a.A + (uint64_t)tid);
+          float u0 = (p.x + 1.f) * 2.3283064365386963e-10f;
+          float u1 = (p.y + 1.f) * 2.3283064365386963e-10f;
+          float eps = sqrtf(-2.f * logf(u0)) * __cosf(6.283185307179586f * u1);
+          a.action[(int64_t)(row0 + r) * a.A + tid] =
+              tanhf(mu[r] + expf(l) * eps) * a.act_limit;
+        }
+      }
+    }
+  }
+}
+
 // learned entropy temperature: one-thread Adam on log_alpha
 // (loss = -log_alpha * (mean_logp + target_entropy))
 __global__ void alpha_update_kernel(float* __restrict__ log_alpha,
@@ -2028,6 +2137,72 @@ void act_fire(int64_t handle) {
                      h.first, h.second);
 }
 
+// Batched acting (evaluation path): rows [0, n) of x[*, O] (row stride
+// x.stride(0)) -> rows [0, n) of action[*, A].  The Philox counter comes
+// from the host by value; deterministic launches ignore it.
+void act_batch(torch::Tensor x, std::vector<torch::Tensor> ws,
+               std::vector<torch::Tensor> bs, torch::Tensor wmu,
+               torch::Tensor bmu, torch::Tensor wls, torch::Tensor bls,
+               torch::Tensor action, int64_t n, bool deterministic,
+               int64_t ctr_val, int64_t seed, double act_limit, double lo,
+               double hi) {
+  auto f32dev = [&](const torch::Tensor& t) {
+    return t.is_cuda() && t.scalar_type() == torch::kFloat32
+        && t.device() == x.device();
+  };
+  ActArgs a{};
+  a.n_layers = (int)ws.size();
+  TORCH_CHECK(a.n_layers >= 1 && a.n_layers <= ACT_MAXL
+              && bs.size() == ws.size(), "act_batch: trunk depth");
+  TORCH_CHECK(f32dev(x) && x.dim() == 2 && x.stride(1) == 1
+              && x.stride(0) >= x.size(1), "act_batch: x must be [N, O] fp32 "
+              "device rows");
+  TORCH_CHECK(f32dev(action) && action.dim() == 2 && action.is_contiguous(),
+              "act_batch: action must be contiguous [N, A] fp32");
+  TORCH_CHECK(n >= 1 && n <= x.size(0) && n <= action.size(0),
+              "act_batch: n outside the x/action buffers");
+  a.x = x.data_ptr<float>();
+  a.O = (int)x.size(1);
+  a.A = (int)action.size(1);
+  TORCH_CHECK(a.O >= 1 && a.O <= ACT_MAXW, "act_batch: obs width > ",
+              ACT_MAXW);
+  TORCH_CHECK(a.A >= 1 && a.A <= 64, "act_batch: act_dim > 64");
+  int K = a.O;
+  for (int L = 0; L < a.n_layers; ++L) {
+    TORCH_CHECK(f32dev(ws[L]) && ws[L].is_contiguous() && ws[L].dim() == 2
+                && ws[L].size(1) == K, "act_batch: trunk weight ", L);
+    a.width[L] = (int)ws[L].size(0);
+    TORCH_CHECK(a.width[L] >= 1 && a.width[L] <= 256,
+                "act_batch: trunk width > 256");
+    TORCH_CHECK(f32dev(bs[L]) && bs[L].is_contiguous()
+                && bs[L].numel() == a.width[L], "act_batch: trunk bias ", L);
+    a.w[L] = ws[L].data_ptr<float>();
+    a.b[L] = bs[L].data_ptr<float>();
+    K = a.width[L];
+  }
+  for (const torch::Tensor* w : {&wmu, &wls})
+    TORCH_CHECK(f32dev(*w) && w->is_contiguous() && w->dim() == 2
+                && w->size(0) == a.A && w->size(1) == K,
+                "act_batch: head weight");
+  for (const torch::Tensor* b : {&bmu, &bls})
+    TORCH_CHECK(f32dev(*b) && b->is_contiguous() && b->numel() == a.A,
+                "act_batch: head bias");
+  a.wmu = wmu.data_ptr<float>();
+  a.bmu = bmu.data_ptr<float>();
+  a.wls = wls.data_ptr<float>();
+  a.bls = bls.data_ptr<float>();
+  a.action = action.data_ptr<float>();
+  a.ctr = nullptr;             // the counter is a launch argument
+  a.seed = (uint64_t)seed;
+  a.act_limit = (float)act_limit;
+  a.lo = (float)lo;
+  a.hi = (float)hi;
+  const int grid = (int)((n + ACTB_R - 1) / ACTB_R);
+  hipLaunchKernelGGL(act_batch_kernel, dim3(grid), dim3(256), 0, stream(),
+                     a, (int)n, (int)x.stride(0), deterministic ? 1 : 0,
+                     (unsigned long long)ctr_val);
+}
+
 void alpha_update(torch::Tensor log_alpha, torch::Tensor alpha_dev,
                   torch::Tensor m, torch::Tensor v, torch::Tensor step,
                   torch::Tensor mean_logp, double target_entropy, double lr) {
@@ -2069,4 +2244,6 @@ void register_fused(pybind11::module_& m) {
   m.def("act_step_pinned", &fused::act_step_pinned);
   m.def("act_prepare", &fused::act_prepare);
   m.def("act_fire", &fused::act_fire);
+  m.def("act_batch", &fused::act_batch,
+        "batched actor forward (deterministic or Philox-stochastic)");
 }
