@@ -2,10 +2,26 @@
 
 Replaces the autograd-recorded update (112 kernels/update, 75% of GPU
 time in scalar-staged GEMMs — profiles/r01_baseline_update_profile.md)
-with an explicit kernel schedule of 26 launches built from the
-multi-problem MFMA kernels in ops/csrc/fused.hip:
+with an explicit kernel schedule of 24 launches at batch 64 (26 with the
+three folds below switched off, 22 with the Adam fold forced on) built
+from the multi-problem MFMA kernels in ops/csrc/fused.hip:
 
  * one Philox counter bump covers the replay draw AND the policy noise;
+   it has no launch of its own: gather2/tg_fwd2 key on ctr+1 and the
+   single-block qloss2, which runs after both, commits ctr and both Adam
+   step counters (TAC_AMD_BUMP_FOLD=0 restores the bump3 launch);
+ * at world=1 a phase's heterogeneous wgrad launch can apply Adam
+   (+polyak, +W^T refresh) itself, replacing the adam_t launch.  By
+   default (TAC_AMD_WGRAD_ADAM=auto) it does so where the launch splits
+   along M — large batch, or fp32 at batch 64 — and the many-block
+   combine kernel carries the update (+6.7% at batch 4096).  Un-split
+   (bf16 batch 64) the update would ride in the tile epilogue of a few
+   dozen blocks; that measured inside the run-to-run spread on the
+   headline, so it needs TAC_AMD_WGRAD_ADAM=1.  =0 never folds; DP runs
+   never fold because the all-reduce sits between wgrad and Adam;
+ * the pi-phase K=1 dgrad of the critic's last layer is never
+   materialised: the next dgrad GEMM forms dqp (x) w_last in registers
+   while staging (TAC_AMD_R1_DGRAD=0 restores the K=1 launch);
  * the replay gather writes states/actions/next-states directly into
    concat-layout buffers (XC = [s|a ; ns|a2], XC2 = [s|pi]) — torch.cat
    never appears;
@@ -14,8 +30,8 @@ multi-problem MFMA kernels in ops/csrc/fused.hip:
    (rows :B, on states) — mathematically identical to the reference's
    two independent draws since the rows are disjoint states;
  * both twin critics run per GEMM launch (blockIdx.z);
- * dgrads are fwd-form GEMMs on cached transposed weights (refreshed in
-   ONE kernel after each Adam step);
+ * dgrads are fwd-form GEMMs on cached transposed weights (refreshed by
+   the launch that applies Adam);
  * wgrads write straight into the FlatAdam gradient buffers;
  * losses are single-block deterministic reductions accumulating into
    device scalars; alpha may live on device and be Adam-updated
@@ -28,6 +44,7 @@ if the communicator refuses capture.  Reference semantics preserved:
 update order, losses and polyak follow sac/algorithm.py:115-162,77-81.
 """
 
+import logging
 import math
 import os
 import typing as t
@@ -38,6 +55,9 @@ from ..buffer.replay import ReplayBuffer
 from ..models.mlp import Actor, DoubleCritic
 from ..optim import FlatAdam
 from ..parallel import comm
+
+
+_log = logging.getLogger(__name__)
 
 
 class FusedSACEngine:
@@ -210,6 +230,39 @@ class FusedSACEngine:
         self._wgrad_batch = (os.environ.get("TAC_AMD_WGRAD_BATCH", "1")
                              == "1" and not self._use_side)
         self._wjobs: t.List[tuple] = []
+        # Adam folded into the phase-wide wgrad launch: only where nothing
+        # sits between the wgrad and Adam (single rank, no collective) and
+        # the phase's dW/db slices tile the optimizer's flat gradient
+        # exactly once (checked per optimizer at the first flush).
+        # "auto" (default) folds only launches that split along M, where
+        # the combine kernel applies the update; "1" also folds un-split
+        # launches (tile epilogue); "0" never folds.
+        adam_flag = os.environ.get("TAC_AMD_WGRAD_ADAM", "auto")
+        self._wgrad_adam_unsplit = adam_flag == "1"
+        self._wgrad_adam = (
+            adam_flag != "0"
+            and self.world == 1 and not self._force_coll
+            # the forced split-graph structure rehearses the
+            # data-parallel schedule, which keeps its adam_t launches
+            and os.environ.get("TAC_AMD_SPLIT_GRAPHS") != "1"
+            and self._wgrad_batch)
+        self._adam_fused: t.Dict[int, bool] = {}
+        # grad slice -> transposed-weight cache, for the fused W^T refresh
+        self._wt_of = {
+            w.grad.data_ptr(): wt
+            for w, wt in zip(self._c_tr_src + self._a_tr_src,
+                             self._c_tr_dst + self._a_tr_dst)}
+        # counter bump committed by qloss2 instead of its own launch
+        self._bump_fold = os.environ.get("TAC_AMD_BUMP_FOLD", "1") != "0"
+        # pi-phase last-layer dgrad as a rank-1 A operand of the next GEMM
+        self._r1_dgrad = (
+            os.environ.get("TAC_AMD_R1_DGRAD", "1") != "0"
+            and len(self.c_w) >= 2 and not self._loss_fuse)
+        if self._r1_dgrad and any(self.cwt[z][-1].data_ptr() % 16
+                                  for z in range(2)):
+            _log.info("engine: rank-1 dgrad operand off (last-layer W^T "
+                      "row is not 16-byte aligned); keeping the K=1 launch")
+            self._r1_dgrad = False
         self._s2 = torch.cuda.Stream()
         self._fork_evs = [torch.cuda.Event() for _ in range(12)]
         self._join_evs = [torch.cuda.Event() for _ in range(4)]
@@ -263,12 +316,55 @@ class FusedSACEngine:
                 list(dys), list(masks), list(xs), list(dws), list(dbs),
                 M, N, K, lddy, ldx, xoff))
 
-    def _wflush(self):
-        """Issue all queued wgrad problems of this phase in ONE launch."""
+    def _adam_covers(self, opt) -> bool:
+        """May this phase's wgrad launch carry opt's Adam step?  Decided
+        once per optimizer from the queued problems."""
+        if not self._wgrad_adam:
+            return False
+        key = id(opt)
+        if key not in self._adam_fused:
+            g = opt.fp.flat_grad
+            base, ranges = g.data_ptr(), []
+            for job in self._wjobs:
+                dw, db = job[3], job[4]
+                ranges.append(((dw.data_ptr() - base) // 4, dw.numel()))
+                ranges.append(((db.data_ptr() - base) // 4, db.numel()))
+            why = None
+            if not 0 < len(self._wjobs) <= 12:
+                why = f"{len(self._wjobs)} wgrad problems (limit 12)"
+            elif not self.ext.ranges_tile_exactly(ranges, g.numel()):
+                why = ("the phase's dW/db slices do not tile the flat "
+                       "gradient exactly once")
+            elif not self._wgrad_adam_unsplit and \
+                    self.ext.mwgrad_het_adam_split(
+                        [j[5] for j in self._wjobs],
+                        [j[6] for j in self._wjobs],
+                        [j[7] for j in self._wjobs]) <= 1:
+                # decided with the compute dtype of the first flush; a
+                # later dtype switch only changes which epilogue runs
+                why = ("the launch does not split along M "
+                       "(TAC_AMD_WGRAD_ADAM=1 folds it anyway)")
+            if why:
+                _log.info("engine: Adam stays in adam_t for the %d-element "
+                          "optimizer: %s", g.numel(), why)
+            self._adam_fused[key] = why is None
+        return self._adam_fused[key]
+
+    def _wflush(self, opt=None, targ=None, rho=0.0):
+        """Issue all queued wgrad problems of this phase in ONE launch;
+        with `opt`, the same launch applies its Adam step where allowed
+        (see _adam_covers) — the caller then skips adam_t."""
         if not self._wjobs:
             return
-        cols = list(zip(*self._wjobs))
-        self.ext.mwgrad_het(*[list(c) for c in cols])
+        cols = [list(c) for c in zip(*self._wjobs)]
+        if opt is not None and self._adam_covers(opt):
+            wts = [self._wt_of.get(dw.data_ptr()) for dw in cols[3]]
+            self.ext.mwgrad_het_adam(
+                *cols, opt.fp.flat, opt.fp.flat_grad, opt.m, opt.v,
+                opt.step_t, opt.lr, opt.betas[0], opt.betas[1], opt.eps,
+                opt.weight_decay, wts, targ, rho)
+        else:
+            self.ext.mwgrad_het(*cols)
         self._wjobs = []
 
     def _mg(self, xs, ws, bs, ys, masks, M, N, K, lda, ldy, relu,
@@ -317,14 +413,18 @@ class FusedSACEngine:
         ext = self.ext
         B, O, A, OC = self.B, self.O, self.A, self.OC
         buf = self.buffer
-        # one launch bumps the replay/noise counter AND both Adam step
-        # counters (their kernels read the committed values later on the
-        # same stream)
-        ext.bump3(self.ctr, self.q_opt.step_t, self.pi_opt.step_t)
+        # the replay/noise counter AND both Adam step counters advance
+        # once per update: either one launch up front, or (folded) the
+        # readers key on ctr+1 and qloss2 commits all three — both Adam
+        # applications run after it on the same stream
+        fold = self._bump_fold
+        ctr_add = 1 if fold else 0
+        if not fold:
+            ext.bump3(self.ctr, self.q_opt.step_t, self.pi_opt.step_t)
         if self.sample:
             ext.gather2(buf.state, buf.actions, buf.rewards, buf.next_state,
                         buf.done, buf._size_dev, self.ctr, self.seed,
-                        self.XC, self.XC2, self.rew, self.done, B)
+                        self.XC, self.XC2, self.rew, self.done, B, ctr_add)
 
         # actor forward over stacked 2B rows of XC[:, :O]
         (wm, bm), (wl, bl) = self.head_w
@@ -355,7 +455,7 @@ class FusedSACEngine:
         # pi rows :B -> XC2[:, O:], a2 rows B: -> XC[B:, O:]
         ext.tg_fwd2(self.hl, self.XC2, O, self.XC, B * self.OCp + O,
                     B, self.logp, self.prob, self.ctr, self.seed,
-                    self.act_limit, self.lo, self.hi)
+                    self.act_limit, self.lo, self.hi, ctr_add)
 
         # target critic on (ns, a2) = XC rows B: AND the live critic on
         # (s, a) = XC rows :B — same shapes, one 4-problem launch per layer
@@ -392,6 +492,8 @@ class FusedSACEngine:
         qt = [self.t_act[z][nL - 1] for z in range(2)]
         # final-layer dgrad (K=1 outer product) fuses into the loss kernel
         fuse = self._loss_fuse
+        bump = ((self.ctr, self.q_opt.step_t, self.pi_opt.step_t)
+                if self._bump_fold else (None, None, None))
         ext.qloss2(q[0], q[1], qt[0], qt[1], self.logp[B:], self.rew,
                    self.done, self.alpha_dev, self.alpha_host,
                    self.loss_q_acc, self.dq[0], self.dq[1], B,
@@ -400,7 +502,7 @@ class FusedSACEngine:
                    self.cwt[1][nL - 1] if fuse else None,
                    self.dc[0][nL - 2] if fuse else None,
                    self.dc[1][nL - 2] if fuse else None,
-                   self.c_w[nL - 2] if fuse else 0)
+                   self.c_w[nL - 2] if fuse else 0, *bump)
 
         # critic backward (wgrad into flat grads; dgrad via cached W^T)
         d = self.dq
@@ -430,19 +532,24 @@ class FusedSACEngine:
                              masks, B, self.c_w[i - 1], self.c_w[i],
                              self.c_w[i], self.c_w[i - 1], False)
                 d = [self.dc[z][i - 1] for z in range(2)]
-        # critic grads must be complete before all-reduce / Adam
-        self._wflush()
+        # critic grads must be complete before all-reduce / Adam; at
+        # world=1 the same launch applies Adam + polyak + W^T refresh
+        # (every critic dgrad that reads the W^T caches is already queued
+        # ahead of it on this stream)
+        self._wflush(self.q_opt, self.target_flat, self.sac.polyak)
         self._join_side()
 
     def _phase_policy(self):
         ext = self.ext
         B, O, A, OC = self.B, self.O, self.A, self.OC
-        # fused Adam + transposed-weight refresh (step already bumped)
+        # fused Adam + transposed-weight refresh (step already bumped) —
+        # unless the critic wgrad launch already applied it
         qo = self.q_opt
-        ext.adam_t(qo.fp.flat, qo.fp.flat_grad, qo.m, qo.v, qo.step_t,
-                   qo.lr, qo.betas[0], qo.betas[1], qo.eps,
-                   qo.weight_decay, self._c_offs, self._c_tr_dst,
-                   self.target_flat, self.sac.polyak)
+        if not self._adam_fused.get(id(qo), False):
+            ext.adam_t(qo.fp.flat, qo.fp.flat_grad, qo.m, qo.v, qo.step_t,
+                       qo.lr, qo.betas[0], qo.betas[1], qo.eps,
+                       qo.weight_decay, self._c_offs, self._c_tr_dst,
+                       self.target_flat, self.sac.polyak)
 
         # critic on (s, pi) = XC2 with the UPDATED critic
         self._critic_fwd(self.XC2, 0, self.cw, self.p_act, self.OCp)
@@ -458,25 +565,46 @@ class FusedSACEngine:
                     self.dcp[1][nL - 2] if fuse else None,
                     self.c_w[nL - 2] if fuse else 0)
 
-        # critic dgrad chain only (frozen critic)
+        # critic dgrad chain only (frozen critic).  The last layer's
+        # dgrad is the outer product dqp (x) w_last (K=1): with r1 it is
+        # never written — the next GEMM forms it while staging its A tile
         d = self.dqp
+        r1 = None
         for i in range(nL - 1, 0, -1):
             masks = [self.p_act[z][i] if i + 1 < nL else None
                      for z in range(2)]
             if i == nL - 1 and fuse:
                 d = [self.dcp[z][i - 1] for z in range(2)]
                 continue
-            self._mg(d, [self.cwt[z][i] for z in range(2)], [None, None],
-                     [self.dcp[z][i - 1] for z in range(2)], masks,
-                     B, self.c_w[i - 1], self.c_w[i], self.c_w[i],
-                     self.c_w[i - 1], False)
+            if i == nL - 1 and self._r1_dgrad:
+                r1 = (list(self.dqp),
+                      [self.cwt[z][nL - 1] for z in range(2)])
+                continue
+            if r1 is not None:
+                ext.mgemm_r1(r1[0], r1[1],
+                             [self.cwt[z][i] for z in range(2)],
+                             [self.dcp[z][i - 1] for z in range(2)], masks,
+                             B, self.c_w[i - 1], self.c_w[i],
+                             self.c_w[i - 1])
+                r1 = None
+            else:
+                self._mg(d, [self.cwt[z][i] for z in range(2)],
+                         [None, None],
+                         [self.dcp[z][i - 1] for z in range(2)], masks,
+                         B, self.c_w[i - 1], self.c_w[i], self.c_w[i],
+                         self.c_w[i - 1], False)
             d = [self.dcp[z][i - 1] for z in range(2)]
         # layer 0: per-critic dxc slabs in one z=2 launch; tg_bwd2 sums
         # them on read (measured faster than the serial two-pass sum2)
         masks0 = [self.p_act[z][0] for z in range(2)]
-        self._mg(d, [self.cwt[z][0] for z in range(2)], [None, None],
-                 [self.dxc, self.dxc2], masks0,
-                 B, OC, self.c_w[0], self.c_w[0], self.OCp, False)
+        if r1 is not None:   # single hidden layer: layer 0 consumes it
+            ext.mgemm_r1(r1[0], r1[1], [self.cwt[z][0] for z in range(2)],
+                         [self.dxc, self.dxc2], masks0, B, OC, self.c_w[0],
+                         self.OCp)
+        else:
+            self._mg(d, [self.cwt[z][0] for z in range(2)], [None, None],
+                     [self.dxc, self.dxc2], masks0,
+                     B, OC, self.c_w[0], self.c_w[0], self.OCp, False)
 
         # actor backward
         ext.tg_bwd2(self.dxc, O, self.dxc2, self.alpha_dev,
@@ -510,18 +638,20 @@ class FusedSACEngine:
                          [mask], B, self.a_hidden[i - 1], self.a_hidden[i],
                          self.a_hidden[i], self.a_hidden[i - 1], False)
                 d = self.da[i - 1]
-        # actor grads must be complete before all-reduce / Adam
-        self._wflush()
+        # actor grads must be complete before all-reduce / Adam (same
+        # launch applies it at world=1; no polyak for the actor)
+        self._wflush(self.pi_opt)
         self._join_side()
 
     def _phase_finish(self):
         ext = self.ext
         po = self.pi_opt
-        ext.adam_t(po.fp.flat, po.fp.flat_grad, po.m, po.v, po.step_t,
-                   po.lr, po.betas[0], po.betas[1], po.eps,
-                   po.weight_decay, self._a_offs, self._a_tr_dst,
-                   None, 0.0)
-        # polyak is fused into the critic adam_t (see _phase_policy)
+        if not self._adam_fused.get(id(po), False):
+            ext.adam_t(po.fp.flat, po.fp.flat_grad, po.m, po.v, po.step_t,
+                       po.lr, po.betas[0], po.betas[1], po.eps,
+                       po.weight_decay, self._a_offs, self._a_tr_dst,
+                       None, 0.0)
+        # polyak is fused into the critic Adam (see _phase_policy)
         if self.learn_alpha:
             ext.alpha_update(self.log_alpha, self.alpha_dev, self.alpha_m,
                              self.alpha_v, self.alpha_step, self.mean_logp,

@@ -25,6 +25,8 @@
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 
+#include <algorithm>
+#include <utility>
 #include <vector>
 
 namespace fused {
@@ -74,6 +76,10 @@ struct MProb {
   const float* x; const float* w; const float* bias; float* y;
   const float* mask;
   const float* x2; const float* w2; const float* mask2;
+  // rank-1 A operand (R1 kernels): x[row][col] = r1_col[row] * r1_row[col]
+  // formed in registers while staging, x itself is never read
+  const float* r1_col;   // [M]
+  const float* r1_row;   // [K], 16-byte aligned
 };
 
 constexpr int MAXZ = 4;
@@ -233,20 +239,35 @@ DEVINL void mma_tiles(const void* xs_, const void* ws_, f32x4 (&acc)[2][2],
 //    instead of 64);
 //  * any ld: 16 lanes per row read consecutive dwords — 4 lines/wave
 //    per instruction instead of 64 scalar-scattered.
-template <bool BF16, bool MASK>
+// R1: the tile element is the fp32 product r1c[row] * r1r[col] (same
+// thread→element map, same masking, one rounding at the LDS write); src
+// is unused.
+template <bool BF16, bool MASK, bool R1 = false>
 DEVINL void load_tile_regs(float* v, const float* src, const float* mask,
-                           int r0, int k0, int R, int C, int ld) {
+                           int r0, int k0, int R, int C, int ld,
+                           const float* r1c = nullptr,
+                           const float* r1r = nullptr) {
   const int tid = threadIdx.x;
   if constexpr (BF16) {
     bool interior = (r0 + 64 <= R) && (k0 + BKP <= C) && ((ld & 3) == 0);
     if (interior) {
       const int row = tid >> 2;          // 4 lanes per row
       const int c = tid & 3;
-      const float* p = src + (int64_t)(r0 + row) * ld + k0 + c * 4;
+      if constexpr (R1) {
+        const float a = r1c[r0 + row];
+        const float* p = r1r + k0 + c * 4;
 #pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        float4 f = *(const float4*)(p + q * 16);
-        v[q*4+0]=f.x; v[q*4+1]=f.y; v[q*4+2]=f.z; v[q*4+3]=f.w;
+        for (int q = 0; q < 8; ++q) {
+          float4 f = *(const float4*)(p + q * 16);
+          v[q*4+0]=a*f.x; v[q*4+1]=a*f.y; v[q*4+2]=a*f.z; v[q*4+3]=a*f.w;
+        }
+      } else {
+        const float* p = src + (int64_t)(r0 + row) * ld + k0 + c * 4;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          float4 f = *(const float4*)(p + q * 16);
+          v[q*4+0]=f.x; v[q*4+1]=f.y; v[q*4+2]=f.z; v[q*4+3]=f.w;
+        }
       }
       if constexpr (MASK) {
         const float* mp = mask + (int64_t)(r0 + row) * ld + k0 + c * 4;
@@ -271,7 +292,8 @@ DEVINL void load_tile_regs(float* v, const float* src, const float* mask,
           const int c = k0 + cc + 16 * q;
           float val = 0.f;
           if (gr < R && c < C) {
-            val = src[(int64_t)gr * ld + c];
+            if constexpr (R1) val = r1c[gr] * r1r[c];
+            else val = src[(int64_t)gr * ld + c];
             if constexpr (MASK)
               val = mask[(int64_t)gr * ld + c] > 0.f ? val : 0.f;
           }
@@ -288,7 +310,8 @@ DEVINL void load_tile_regs(float* v, const float* src, const float* mask,
       int c = k0 + c0 + e;
       float val = 0.f;
       if (gr < R && c < C) {
-        val = src[(int64_t)gr * ld + c];
+        if constexpr (R1) val = r1c[gr] * r1r[c];
+        else val = src[(int64_t)gr * ld + c];
         if constexpr (MASK)
           val = mask[(int64_t)gr * ld + c] > 0.f ? val : 0.f;
       }
@@ -365,23 +388,26 @@ DEVINL void mma_tiles_p(const void* xs_, const void* ws_,
   }
 }
 
-template <bool BF16, bool MASK>
+template <bool BF16, bool MASK, bool R1 = false>
 DEVINL void gemm_pass(const float* x, const float* w, const float* mask,
                       int M, int N, int K, int lda, int ldw,
                       void* xs, void* ws,
                       int bm0, int bn0, int lane, int wrow, int wcol,
-                      int tid, f32x4 (&acc)[2][2]) {
+                      int tid, f32x4 (&acc)[2][2],
+                      const float* r1c = nullptr,
+                      const float* r1r = nullptr) {
   constexpr int BK = BF16 ? BKP : BKF2;
   constexpr int EL = BF16 ? 32 : 4;
   float va[EL], vb[EL];
   (void)tid;
-  load_tile_regs<BF16, MASK>(va, x, mask, bm0, 0, M, K, lda);
+  load_tile_regs<BF16, MASK, R1>(va, x, mask, bm0, 0, M, K, lda, r1c, r1r);
   load_tile_regs<BF16, false>(vb, w, nullptr, bn0, 0, N, K, ldw);
   for (int k0 = 0; k0 < K; k0 += BK) {
     write_tile_lds<BF16>(xs, va, bm0, k0, M, K, lda);
     write_tile_lds<BF16>(ws, vb, bn0, k0, N, K, ldw);
     if (k0 + BK < K) {
-      load_tile_regs<BF16, MASK>(va, x, mask, bm0, k0 + BK, M, K, lda);
+      load_tile_regs<BF16, MASK, R1>(va, x, mask, bm0, k0 + BK, M, K, lda,
+                                     r1c, r1r);
       load_tile_regs<BF16, false>(vb, w, nullptr, bn0, k0 + BK, N, K,
                                   ldw);
     }
@@ -479,7 +505,7 @@ void mgemm_nt_kernel(MGemm g) {
         }
 }
 
-template <bool BF16, bool MASK, bool RELU, bool SUM2>
+template <bool BF16, bool MASK, bool RELU, bool SUM2, bool R1 = false>
 __global__ __launch_bounds__(256)
 void mgemm_kernel(MGemm g) {
   const int zz = g.part ? ((int)blockIdx.z % g.nz) : (int)blockIdx.z;
@@ -501,10 +527,15 @@ void mgemm_kernel(MGemm g) {
   const int k_len = g.part ? min(g.K - k_lo, g.k_chunk) : g.K;
 
   f32x4 acc[2][2] = {};
-  gemm_pass<BF16, MASK>(p.x + k_lo, p.w + k_lo,
-                        p.mask ? p.mask + k_lo : nullptr,
-                        g.M, g.N, k_len, g.lda, g.K, xs, ws,
-                        bm0, bn0, lane, wrow, wcol, tid, acc);
+  if constexpr (R1)   // never split-K (host gate): k_lo = 0
+    gemm_pass<BF16, MASK, true>(nullptr, p.w, p.mask, g.M, g.N, g.K, g.lda,
+                                g.K, xs, ws, bm0, bn0, lane, wrow, wcol,
+                                tid, acc, p.r1_col, p.r1_row);
+  else
+    gemm_pass<BF16, MASK>(p.x + k_lo, p.w + k_lo,
+                          p.mask ? p.mask + k_lo : nullptr,
+                          g.M, g.N, k_len, g.lda, g.K, xs, ws,
+                          bm0, bn0, lane, wrow, wcol, tid, acc);
   if constexpr (SUM2) {  // split-K never combines with SUM2 (host gate)
     gemm_pass<BF16, MASK>(p.x2, p.w2, p.mask2, g.M, g.N, g.K2, g.K2,
                           g.K2, xs, ws, bm0, bn0, lane, wrow, wcol, tid,
@@ -555,6 +586,77 @@ void mgemm_combine_kernel(MGemm g, int split, bool relu) {
     if (relu) s = fmaxf(s, 0.f);
     p.y[(int64_t)m * g.ldy + n] = s;
   }
+}
+
+// ---------------------------------------------------------------------------
+// The per-element Adam update, shared by adam_t_kernel and the wgrad
+// epilogues that apply Adam to the gradient they just finished
+// (mwgrad_het_adam): m, v, p and the optional polyak target at flat
+// index i.  Returns the new parameter so the caller can also place it in
+// a transposed-weight cache.
+// ---------------------------------------------------------------------------
+
+// arithmetic only: m and v are updated in place, the new parameter is
+// returned.  Callers that own many elements load them all first, so the
+// memory latencies overlap instead of chaining element by element.
+DEVINL float adam_math(float g, float p, float& m, float& v, float lr,
+                       float b1, float b2, float eps, float wd, float bc1,
+                       float bc2) {
+  // The roundings are spelled out (three fused multiply-adds, nothing
+  // else contracted) so every kernel that inlines this gives the same
+  // bits: left to the compiler, the choice varied with the surrounding
+  // code, and a last-bit difference in m grows over bf16 updates.
+#pragma clang fp contract(off)
+  float gi = __builtin_fmaf(wd, p, g);
+  float mi = __builtin_fmaf(b1, m, (1.f - b1) * gi);
+  float vi = __builtin_fmaf(b2, v, ((1.f - b2) * gi) * gi);
+  m = mi;
+  v = vi;
+  return p - lr / bc1 * mi / (sqrtf(vi / bc2) + eps);
+}
+
+// polyak target tracking of the post-Adam parameter — replaces the
+// standalone polyak launch (reference semantics: the target averages
+// the q_opt.step()-updated critic, and nothing mutates critic params
+// between Adam and update_targets, sac/algorithm.py:139,278)
+DEVINL float polyak_math(float targ, float pn, float rho) {
+#pragma clang fp contract(off)
+  return rho * targ + (1.f - rho) * pn;
+}
+
+DEVINL float adam_elem(float* __restrict__ p, float* __restrict__ m,
+                       float* __restrict__ v, float* __restrict__ targ,
+                       int64_t i, float g, float lr, float b1, float b2,
+                       float eps, float wd, float bc1, float bc2,
+                       float rho) {
+  float mi = m[i], vi = v[i];
+  const float pn = adam_math(g, p[i], mi, vi, lr, b1, b2, eps, wd, bc1,
+                             bc2);
+  m[i] = mi;
+  v[i] = vi;
+  p[i] = pn;
+  if (targ) targ[i] = polyak_math(targ[i], pn, rho);
+  return pn;
+}
+
+// Adam state for the wgrad kernels that update in their epilogue.  All
+// pointers are flat-buffer bases; a problem's flat offset is
+// dw - grad (db - grad for its bias).
+constexpr int MAXW = 12;   // problems per heterogeneous wgrad launch
+struct WAdam {
+  float* p; float* m; float* v; float* targ;   // targ may be null
+  const float* grad;
+  const int64_t* step;
+  float lr, b1, b2, eps, wd, rho;
+  float* wt[MAXW];   // per-problem transposed-weight cache [K,N] or null
+  int quarter;       // 1: four blocks per tile, a quarter epilogue each
+                     // (host sets it only for single-K-step launches)
+};
+
+DEVINL float wadam_apply(const WAdam& ad, int64_t i, float g, float bc1,
+                         float bc2) {
+  return adam_elem(ad.p, ad.m, ad.v, ad.targ, i, g, ad.lr, ad.b1, ad.b2,
+                   ad.eps, ad.wd, bc1, bc2, ad.rho);
 }
 
 // ---------------------------------------------------------------------------
@@ -634,7 +736,24 @@ DEVINL void wstage_bf16(__bf16* dst, const float* __restrict__ src,
   }
 }
 
-template <bool BF16, bool MASK>
+// ADAM: with do_adam the tile epilogue also applies Adam to every
+// (gn, gk) element it owns (`wt` = this problem's [K,N] transposed cache or
+// null).  Hazard argument: the wgrad kernels read only dy, masks,
+// activations and XC — never a weight, a W^T cache or the target
+// buffer — and every flat element belongs to exactly one tile (host
+// coverage gate), so writing p/m/v/target/W^T here cannot race within
+// the kernel; the next reader is a later launch on the same stream.
+// q >= 0 (WAdam::quarter): this block owns only the (mi, ni) =
+// (q >> 1, q & 1) 16x16 sub-tile of every wave — four blocks share one
+// 64x64 tile.  Adam's divisions and square root are ALU-heavy; on the few
+// dozen blocks of a batch-64 phase they cost more than the adam_t launch
+// they replace (measured 14 us against 5.2 + 5.7), so the epilogue is
+// spread over 4x the blocks.  Each of the four blocks repeats the tile's
+// whole staging + MFMA loop (so the gradient bits do not depend on q);
+// that is only cheap when the loop is ONE K-step, and the launcher sets
+// quarter for exactly that case.  Any longer un-split launch runs q = -1:
+// one block per tile, all 16 elements per thread.
+template <bool BF16, bool MASK, bool ADAM = false>
 DEVINL void wgrad_tile_body(const float* __restrict__ dy,
                             const float* __restrict__ ymask,
                             const float* __restrict__ x,
@@ -642,7 +761,9 @@ DEVINL void wgrad_tile_body(const float* __restrict__ dy,
                             float* __restrict__ db_out, bool has_db,
                             int M, int N, int K, int lddy, int ldx,
                             int m_lo, int m_hi, int bn0, int bk0,
-                            char* smem, float* dbs) {
+                            char* smem, float* dbs,
+                            const WAdam& ad = WAdam{}, bool do_adam = false,
+                            float* __restrict__ wt = nullptr, int q = -1) {
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wid = tid >> 6;
@@ -653,6 +774,41 @@ DEVINL void wgrad_tile_body(const float* __restrict__ dy,
 
   if (tid < 64) dbs[tid] = 0.f;
   f32x4 acc[2][2] = {};
+
+  // ADAM: the optimizer state of all 16 owned elements is requested
+  // before the staging loop, so its memory latency overlaps the dy/x
+  // loads and the MFMAs instead of following them, and no load waits on
+  // another element's store (the launch is a few dozen blocks: latency,
+  // not bandwidth, is what the epilogue costs).
+  float pv[2][2][4] = {}, mv[2][2][4] = {}, vv[2][2][4] = {},
+        tv[2][2][4] = {};
+  float bc1 = 1.f, bc2 = 1.f;
+  if constexpr (ADAM) {
+    if (do_adam) {
+      const float t = (float)ad.step[0];
+      bc1 = 1.f - powf(ad.b1, t);
+      bc2 = 1.f - powf(ad.b2, t);
+      const int64_t fo = dw_out - ad.grad;
+      const int crow = (lane >> 4) * 4, ccol = lane & 15;
+#pragma unroll
+      for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int gn = bn0 + wrow + mi * 16 + crow + r;
+            const int gk = bk0 + wcol + ni * 16 + ccol;
+            const bool own = q < 0 || q == mi * 2 + ni;
+            if (own && gn < N && gk < K) {
+              const int64_t i = fo + (int64_t)gn * K + gk;
+              pv[mi][ni][r] = ad.p[i];
+              mv[mi][ni][r] = ad.m[i];
+              vv[mi][ni][r] = ad.v[i];
+              if (ad.targ) tv[mi][ni][r] = ad.targ[i];
+            }
+          }
+    }
+  }
 
   for (int i0 = m_lo; i0 < m_hi; i0 += BK) {
     // A tile: as[n][i] = dYeff[i0+i][bn0+n]; staged transposed.
@@ -725,11 +881,53 @@ DEVINL void wgrad_tile_body(const float* __restrict__ dy,
       for (int r = 0; r < 4; ++r) {
         int gn = bn0 + wrow + mi * 16 + crow + r;
         int gk = bk0 + wcol + ni * 16 + ccol;
+        if (ADAM && q >= 0 && q != mi * 2 + ni) continue;
         if (gn < N && gk < K)
           dw_out[(int64_t)gn * K + gk] = acc[mi][ni][r];
       }
+  if (ADAM && q > 0) db_out = nullptr;   // quarter 0 owns the bias
   if (db_out && bk0 == 0 && tid < 64 && bn0 + tid < N)
     db_out[bn0 + tid] = dbs[tid];
+  if constexpr (ADAM) {
+    if (!do_adam) return;   // split-M: the combine applies Adam
+    const int64_t fo = dw_out - ad.grad;
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+      for (int ni = 0; ni < 2; ++ni) {
+        const int gn0 = bn0 + wrow + mi * 16 + crow;
+        const int gk = bk0 + wcol + ni * 16 + ccol;
+        if (gk >= K || (q >= 0 && q != mi * 2 + ni)) continue;
+        float pn[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (gn0 + r < N) {
+            const int64_t i = fo + (int64_t)(gn0 + r) * K + gk;
+            pn[r] = adam_math(acc[mi][ni][r], pv[mi][ni][r], mv[mi][ni][r],
+                              vv[mi][ni][r], ad.lr, ad.b1, ad.b2, ad.eps,
+                              ad.wd, bc1, bc2);
+            ad.m[i] = mv[mi][ni][r];
+            ad.v[i] = vv[mi][ni][r];
+            ad.p[i] = pn[r];
+            if (ad.targ)
+              ad.targ[i] = polyak_math(tv[mi][ni][r], pn[r], ad.rho);
+          }
+        if (wt) {
+          // the four r rows are consecutive gn: one 16-byte W^T store
+          // where it is in bounds and aligned
+          float* dst = wt + (int64_t)gk * N + gn0;
+          if (gn0 + 3 < N && ((uintptr_t)dst & 15) == 0) {
+            *(float4*)dst = make_float4(pn[0], pn[1], pn[2], pn[3]);
+          } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              if (gn0 + r < N) dst[r] = pn[r];
+          }
+        }
+      }
+    if (db_out && bk0 == 0 && tid < 64 && bn0 + tid < N)
+      wadam_apply(ad, (db_out - ad.grad) + bn0 + tid, dbs[tid], bc1, bc2);
+  }
 }
 
 template <bool BF16, bool MASK>
@@ -765,7 +963,6 @@ void mwgrad_kernel(WGemm g) {
 // No split-M (phase batches are small); fully deterministic.
 // ---------------------------------------------------------------------------
 
-constexpr int MAXW = 12;
 struct WHProb {
   const float* dy; const float* ymask; const float* x;
   float* dw; float* db;
@@ -866,13 +1063,18 @@ DEVINL void wgrad_tile_body2(const WHProb& p, float* dw_out,
     db_out[bn0 + tid] = dbs[tid];
 }
 
-template <bool BF16>
-__global__ __launch_bounds__(256)
-void mwgrad_het_kernel(WHArgs a) {
+template <bool BF16, bool ADAM = false>
+DEVINL void mwgrad_het_body(const WHArgs& a, const WAdam& ad) {
   constexpr int LBYTES = BF16 ? (64 * LDSB2 * 2) : (64 * LDSF2 * 4);
   __shared__ __attribute__((aligned(16))) char smem[4 * LBYTES];
   __shared__ float dbs[128];
   int b = (int)blockIdx.x;
+  int q = -1;
+  if constexpr (ADAM) {
+    // single-K-step un-split launch: four blocks per tile, one 16x16
+    // quarter of each wave's sub-tiles each (see wgrad_tile_body)
+    if (ad.quarter) { q = b & 3; b >>= 2; }
+  }
   if (a.xcd_chunk) {
     // chunk-per-XCD remap: hardware places wgid on XCD wgid%8 (block
     // count is padded to a multiple of 8), so chunk i of the clustered
@@ -911,13 +1113,29 @@ void mwgrad_het_kernel(WHArgs a) {
     m_lo = (int)blockIdx.z * a.m_chunk;
     m_hi = min(p.M, m_lo + a.m_chunk);
   }
-  if (BF16 && (p.rn > 1 || p.rk > 1)) {
+  if (!ADAM && BF16 && (p.rn > 1 || p.rk > 1)) {
     if (p.ymask)
       wgrad_tile_body2<true>(p, dw_out, db_out, m_lo, m_hi, bn0, bk0,
                              smem, dbs);
     else
       wgrad_tile_body2<false>(p, dw_out, db_out, m_lo, m_hi, bn0, bk0,
                               smem, dbs);
+    return;
+  }
+  if constexpr (ADAM) {
+    // split-M slabs hold partial sums: Adam runs in the combine instead
+    const bool do_adam = a.part == nullptr;
+    float* wt = ad.wt[zi];
+    if (p.ymask)
+      wgrad_tile_body<BF16, true, true>(
+          p.dy, p.ymask, p.x, dw_out, db_out, p.db != nullptr, p.M, p.N,
+          p.K, p.lddy, p.ldx, m_lo, m_hi, bn0, bk0, smem, dbs, ad,
+          do_adam, wt, q);
+    else
+      wgrad_tile_body<BF16, false, true>(
+          p.dy, p.ymask, p.x, dw_out, db_out, p.db != nullptr, p.M, p.N,
+          p.K, p.lddy, p.ldx, m_lo, m_hi, bn0, bk0, smem, dbs, ad,
+          do_adam, wt, q);
     return;
   }
   if (p.ymask)
@@ -930,9 +1148,32 @@ void mwgrad_het_kernel(WHArgs a) {
                                  p.ldx, m_lo, m_hi, bn0, bk0, smem, dbs);
 }
 
-// one deterministic combine for EVERY problem of the phase
+template <bool BF16>
 __global__ __launch_bounds__(256)
-void mwgrad_het_combine_kernel(WHArgs a, int split) {
+void mwgrad_het_kernel(WHArgs a) {
+  mwgrad_het_body<BF16, false>(a, WAdam{});
+}
+
+// wgrad + Adam in one launch (mwgrad_het_adam): own instantiations, the
+// plain kernels above keep their code
+template <bool BF16>
+__global__ __launch_bounds__(256)
+void mwgrad_het_adam_kernel(WHArgs a, WAdam ad) {
+  mwgrad_het_body<BF16, true>(a, ad);
+}
+
+// one deterministic combine for EVERY problem of the phase; ADAM also
+// applies the update to each summed element (same hazard argument as the
+// tile epilogue: one thread owns each flat element)
+template <bool ADAM>
+DEVINL void mwgrad_het_combine_body(const WHArgs& a, int split,
+                                    const WAdam& ad) {
+  float bc1 = 1.f, bc2 = 1.f;
+  if constexpr (ADAM) {
+    const float t = (float)ad.step[0];
+    bc1 = 1.f - powf(ad.b1, t);
+    bc2 = 1.f - powf(ad.b2, t);
+  }
   const int64_t total = a.per_slab;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -949,7 +1190,30 @@ void mwgrad_het_combine_kernel(WHArgs a, int split) {
     const int64_t dwn = (int64_t)p.N * p.K;
     if (off < dwn) p.dw[off] = s;
     else if (p.db) p.db[off - dwn] = s;
+    if constexpr (ADAM) {
+      if (off < dwn) {
+        const float pn = wadam_apply(ad, (p.dw - ad.grad) + off, s, bc1,
+                                     bc2);
+        if (float* wt = ad.wt[zi]) {
+          const int nn = (int)(off / p.K);
+          const int kk = (int)(off - (int64_t)nn * p.K);
+          wt[(int64_t)kk * p.N + nn] = pn;
+        }
+      } else if (p.db) {
+        wadam_apply(ad, (p.db - ad.grad) + (off - dwn), s, bc1, bc2);
+      }
+    }
   }
+}
+
+__global__ __launch_bounds__(256)
+void mwgrad_het_combine_kernel(WHArgs a, int split) {
+  mwgrad_het_combine_body<false>(a, split, WAdam{});
+}
+
+__global__ __launch_bounds__(256)
+void mwgrad_het_combine_adam_kernel(WHArgs a, int split, WAdam ad) {
+  mwgrad_het_combine_body<true>(a, split, ad);
 }
 
 // deterministic combine of split-M wgrad slabs: for each problem z,
@@ -1042,14 +1306,15 @@ void gather2_kernel(const float* __restrict__ state,
                     const float* __restrict__ nstate,
                     const float* __restrict__ done,
                     const int64_t* __restrict__ size_dev,
-                    const int64_t* __restrict__ ctr, uint64_t seed,
+                    const int64_t* __restrict__ ctr, int64_t ctr_add,
+                    uint64_t seed,
                     float* __restrict__ xc,   // [2B, ldc]
                     float* __restrict__ xc2,  // [B, ldc]
                     float* __restrict__ orew, float* __restrict__ od,
                     int B, int obs_dim, int act_dim, int ldc) {
   const int j = blockIdx.x;
   const uint64_t size = (uint64_t)size_dev[0];
-  P4 r = philox_(seed, (uint64_t)ctr[0], (uint64_t)j);
+  P4 r = philox_(seed, (uint64_t)(ctr[0] + ctr_add), (uint64_t)j);
   uint64_t u = ((uint64_t)r.x << 32) | r.y;
   int64_t idx = (int64_t)(u % (size ? size : 1));
 
@@ -1080,7 +1345,8 @@ void tg_fwd2_kernel(const float* __restrict__ hl,  // [R, 2A]: mu | log_std
                     float* __restrict__ out0, int ld0,
                     float* __restrict__ out1, int ld1, int B0,
                     float* __restrict__ logp, float* __restrict__ prob_out,
-                    const int64_t* __restrict__ ctr, uint64_t seed,
+                    const int64_t* __restrict__ ctr, int64_t ctr_add,
+                    uint64_t seed,
                     int R, int A, float act_limit, float lo, float hi) {
   const int b = blockIdx.x;
   const int a = threadIdx.x;
@@ -1088,8 +1354,8 @@ void tg_fwd2_kernel(const float* __restrict__ hl,  // [R, 2A]: mu | log_std
   if (a < A) {
     const int64_t i = (int64_t)b * A + a;
     // philox noise: one draw per element (use lane of the quad)
-    P4 r = philox_(seed ^ 0x517cc1b727220a95ull, (uint64_t)ctr[0],
-                   (uint64_t)i);
+    P4 r = philox_(seed ^ 0x517cc1b727220a95ull,
+                   (uint64_t)(ctr[0] + ctr_add), (uint64_t)i);
     float u0 = (r.x + 1.f) * 2.3283064365386963e-10f;
     float u1 = (r.y + 1.f) * 2.3283064365386963e-10f;
     float eps = sqrtf(-2.f * logf(u0)) * __cosf(6.283185307179586f * u1);
@@ -1190,11 +1456,20 @@ void qloss2_kernel(const float* __restrict__ q1, const float* __restrict__ q2,
                    const float* __restrict__ wt3_0,
                    const float* __restrict__ wt3_1,
                    float* __restrict__ dy2_0, float* __restrict__ dy2_1,
-                   int h2) {
+                   int h2,
+                   int64_t* __restrict__ bump0, int64_t* __restrict__ bump1,
+                   int64_t* __restrict__ bump2) {
   __shared__ float red[4];
   __shared__ float dqs[2][LOSS_MAXB];
   const float alpha = alpha_dev ? alpha_dev[0] : alpha_host;
   const bool fuse = dy2_0 != nullptr;
+  // counters are read up front so their latency hides under the loss
+  int64_t c0 = 0, c1 = 0, c2 = 0;
+  if (threadIdx.x == 0) {
+    if (bump0) c0 = bump0[0];
+    if (bump1) c1 = bump1[0];
+    if (bump2) c2 = bump2[0];
+  }
   float acc = 0.f;
   for (int i = threadIdx.x; i < B; i += blockDim.x) {
     float backup = scale * rew[i] + gamma * (1.f - done[i]) *
@@ -1210,8 +1485,15 @@ void qloss2_kernel(const float* __restrict__ q1, const float* __restrict__ q2,
   for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
-  if (threadIdx.x == 0)
+  if (threadIdx.x == 0) {
     loss_acc[0] += (red[0] + red[1] + red[2] + red[3]) / B;
+    // commit the update's counter bump (replay/noise counter + both Adam
+    // step counters): this single block runs after both counter readers
+    // (gather2 / tg_fwd2 key on ctr+1) and before both Adam applications
+    if (bump0) bump0[0] = c0 + 1;
+    if (bump1) bump1[0] = c1 + 1;
+    if (bump2) bump2[0] = c2 + 1;
+  }
   if (fuse) {
     const int64_t total = (int64_t)B * h2;
     for (int64_t idx = threadIdx.x; idx < total; idx += blockDim.x) {
@@ -1522,19 +1804,8 @@ void adam_t_kernel(float* __restrict__ p, const float* __restrict__ g,
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += stride) {
-    float gi = g[i] + wd * p[i];
-    float mi = b1 * m[i] + (1.f - b1) * gi;
-    float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-    m[i] = mi;
-    v[i] = vi;
-    float pn = p[i] - lr / bc1 * mi / (sqrtf(vi / bc2) + eps);
-    p[i] = pn;
-    // fused polyak target tracking of the post-Adam parameters —
-    // replaces the standalone polyak launch (reference semantics: the
-    // target averages the q_opt.step()-updated critic, and nothing
-    // mutates critic params between Adam and update_targets,
-    // sac/algorithm.py:139,278)
-    if (targ) targ[i] = rho * targ[i] + (1.f - rho) * pn;
+    const float pn = adam_elem(p, m, v, targ, i, g[i], lr, b1, b2, eps, wd,
+                               bc1, bc2, rho);
     // slabs are offset-sorted (host contract): early-break keeps the
     // per-element search ~O(matching slab); 32-bit local math (weight
     // slabs are < 2^31 elements)
@@ -1686,6 +1957,52 @@ void mgemm(std::vector<torch::Tensor> xs, std::vector<torch::Tensor> ws,
   }
 }
 
+// mgemm with a rank-1 A operand: y_z = mask_z(cols_z ⊗ rows_z) @ w_z^T.
+// Replaces a K=1 GEMM that only materialised the outer product for the
+// next GEMM's staging to read back.  masks are [M, K] contiguous.
+void mgemm_r1(std::vector<torch::Tensor> cols,
+              std::vector<torch::Tensor> rows,
+              std::vector<torch::Tensor> ws, std::vector<torch::Tensor> ys,
+              std::vector<torch::Tensor> masks,
+              int64_t M, int64_t N, int64_t K, int64_t ldy) {
+  const int nz = (int)cols.size();
+  TORCH_CHECK(nz >= 1 && nz <= MAXZ && (int)rows.size() == nz
+              && (int)ws.size() == nz && (int)ys.size() == nz
+              && (int)masks.size() == nz, "mgemm_r1: 1..4 problems");
+  TORCH_CHECK(M >= 1 && N >= 1 && K >= 1 && ldy >= N, "mgemm_r1: shape");
+  MGemm g{};
+  g.M = (int)M; g.N = (int)N; g.K = (int)K;
+  g.lda = (int)K; g.ldy = (int)ldy;
+  g.nz = nz; g.k_chunk = (int)K; g.part = nullptr;
+  for (int z = 0; z < nz; ++z) {
+    auto f32c = [](const torch::Tensor& t) {
+      return t.is_contiguous() && t.scalar_type() == torch::kFloat32;
+    };
+    TORCH_CHECK(f32c(cols[z]) && cols[z].numel() == M, "mgemm_r1: col ", z);
+    TORCH_CHECK(f32c(rows[z]) && rows[z].numel() == K
+                && ((uintptr_t)rows[z].data_ptr<float>() & 15) == 0,
+                "mgemm_r1: row ", z, " must be K floats, 16-byte aligned");
+    TORCH_CHECK(f32c(ws[z]) && ws[z].numel() == N * K, "mgemm_r1: w ", z);
+    TORCH_CHECK(f32c(masks[z]) && masks[z].numel() == M * K,
+                "mgemm_r1: mask ", z);
+    TORCH_CHECK(ys[z].scalar_type() == torch::kFloat32
+                && ys[z].numel() >= (M - 1) * ldy + N, "mgemm_r1: y ", z);
+    g.p[z].r1_col = cols[z].data_ptr<float>();
+    g.p[z].r1_row = rows[z].data_ptr<float>();
+    g.p[z].w = ws[z].data_ptr<float>();
+    g.p[z].y = ys[z].data_ptr<float>();
+    g.p[z].mask = masks[z].data_ptr<float>();
+  }
+  dim3 grid((unsigned)((M + TB - 1) / TB), (unsigned)((N + TB - 1) / TB),
+            nz);
+  if (*g_bf16_flag)
+    hipLaunchKernelGGL((mgemm_kernel<true, true, false, false, true>), grid,
+                       dim3(256), 0, stream(), g);
+  else
+    hipLaunchKernelGGL((mgemm_kernel<false, true, false, false, true>),
+                       grid, dim3(256), 0, stream(), g);
+}
+
 void mwgrad(std::vector<torch::Tensor> dys,
             std::vector<c10::optional<torch::Tensor>> ymasks,
             std::vector<torch::Tensor> xs,
@@ -1744,14 +2061,60 @@ void mwgrad(std::vector<torch::Tensor> dys,
   }
 }
 
-void mwgrad_het(std::vector<torch::Tensor> dys,
-                std::vector<c10::optional<torch::Tensor>> ymasks,
-                std::vector<torch::Tensor> xs,
-                std::vector<torch::Tensor> dws,
-                std::vector<torch::Tensor> dbs,
-                std::vector<int64_t> Ms, std::vector<int64_t> Ns,
-                std::vector<int64_t> Ks, std::vector<int64_t> lddys,
-                std::vector<int64_t> ldxs, std::vector<int64_t> x_offs) {
+static bool het_xcd() {   // XCD-clustered enumeration flag (read once)
+  static int xcd_env = []{
+    const char* e = getenv("TAC_AMD_WGRAD_XCD");
+    return e ? atoi(e) : 0;
+  }();
+  return xcd_env == 1;
+}
+
+// split-M plan of a heterogeneous wgrad launch of `blk` tiles whose
+// deepest problem has maxM rows: slabs along M, rows per slab, and the
+// K-steps of the whole M (chunks)
+struct HetSplit { int split, m_chunk, chunks; };
+static HetSplit het_split(int maxM, int blk) {
+  const int BKc = *g_bf16_flag ? BKB2 : BKF2;
+  const int chunks = (maxM + BKc - 1) / BKc;
+  int split = std::max(1, std::min({chunks, (384 + blk - 1) / blk, 64}));
+  const int m_chunk = ((maxM + split - 1) / split + BKc - 1) / BKc * BKc;
+  split = (maxM + m_chunk - 1) / m_chunk;
+  return {split, m_chunk, chunks};
+}
+
+// Host-only: how many M slabs mwgrad_het_adam would use for these shapes
+// in the current compute dtype (> 1: the combine kernel applies Adam over
+// many blocks; 1: the tile epilogue does).
+int64_t mwgrad_het_adam_split(std::vector<int64_t> Ms,
+                              std::vector<int64_t> Ns,
+                              std::vector<int64_t> Ks) {
+  const bool xcd = het_xcd();
+  int blk = 0, maxM = 0;
+  for (size_t i = 0; i < Ms.size(); ++i) {
+    const int bx = (int)((Ns[i] + TB - 1) / TB);
+    const int bk_t = (int)((Ks[i] + TB - 1) / TB);
+    if (xcd) {
+      const int cn = std::min(2, bx), ck = std::min(2, bk_t);
+      blk += ((bx + cn - 1) / cn) * ((bk_t + ck - 1) / ck) * cn * ck;
+    } else {
+      blk += bx * bk_t;
+    }
+    maxM = std::max(maxM, (int)Ms[i]);
+  }
+  return blk ? het_split(maxM, blk).split : 1;
+}
+
+// `ad` non-null: launch the Adam-carrying instantiations (the 128x128
+// sub-tiled body has no Adam epilogue, so that knob is ignored there)
+static void mwgrad_het_impl(std::vector<torch::Tensor>& dys,
+                std::vector<c10::optional<torch::Tensor>>& ymasks,
+                std::vector<torch::Tensor>& xs,
+                std::vector<torch::Tensor>& dws,
+                std::vector<torch::Tensor>& dbs,
+                std::vector<int64_t>& Ms, std::vector<int64_t>& Ns,
+                std::vector<int64_t>& Ks, std::vector<int64_t>& lddys,
+                std::vector<int64_t>& ldxs, std::vector<int64_t>& x_offs,
+                const WAdam* ad) {
   const int np = (int)dys.size();
   TORCH_CHECK(np >= 1 && np <= MAXW, "mwgrad_het: 1..12 problems");
   WHArgs a{};
@@ -1759,12 +2122,7 @@ void mwgrad_het(std::vector<torch::Tensor> dys,
   int blk = 0;
   int64_t poff = 0;
   int maxM = 0;
-  // XCD-clustered enumeration flag (read once)
-  static int xcd_env = []{
-    const char* e = getenv("TAC_AMD_WGRAD_XCD");
-    return e ? atoi(e) : 0;
-  }();
-  const bool xcd = xcd_env == 1;
+  const bool xcd = het_xcd();
   for (int i = 0; i < np; ++i) {
     WHProb& p = a.p[i];
     p.dy = dys[i].data_ptr<float>();
@@ -1785,7 +2143,8 @@ void mwgrad_het(std::vector<torch::Tensor> dys,
       const char* e = getenv("TAC_AMD_WGRAD_RNRK");
       return e ? atoi(e) : 0;
     }();
-    const bool big = rnrk_env == 1 && *g_bf16_flag && p.M >= 1024;
+    const bool big = rnrk_env == 1 && *g_bf16_flag && p.M >= 1024
+                     && ad == nullptr;
     p.rn = (big && p.N >= 128) ? 2 : 1;
     p.rk = (big && p.K >= 128) ? 2 : 1;
     p.bx = (p.N + TB * p.rn - 1) / (TB * p.rn);
@@ -1816,12 +2175,9 @@ void mwgrad_het(std::vector<torch::Tensor> dys,
   // split-M across blockIdx.z at large batch (mirrors mwgrad's split;
   // ONE combine covers every problem of the phase)
   const bool bf16 = *g_bf16_flag;
-  const int BKc = bf16 ? BKB2 : BKF2;
-  const int chunks = (maxM + BKc - 1) / BKc;
-  int split = std::max(1, std::min({chunks, (384 + blk - 1) / blk, 64}));
-  int m_chunk = ((maxM + split - 1) / split + BKc - 1) / BKc * BKc;
-  split = (maxM + m_chunk - 1) / m_chunk;
-  a.m_chunk = m_chunk;
+  const HetSplit hs = het_split(maxM, blk);
+  const int split = hs.split;
+  a.m_chunk = hs.m_chunk;
   a.per_slab = poff;
   a.part = nullptr;
   torch::Tensor part;
@@ -1830,7 +2186,22 @@ void mwgrad_het(std::vector<torch::Tensor> dys,
     a.part = part.data_ptr<float>();
   }
   dim3 grid(grid_x, 1, split);
-  if (bf16)
+  WAdam adk{};
+  if (ad) {
+    adk = *ad;
+    // Quarter epilogues (four blocks per tile) only where repeating the
+    // tile's staging + MFMA loop four times is cheap: the whole M is ONE
+    // K-step.  A longer un-split launch (>= 384 tiles at any M) keeps one
+    // block per tile and the full 16-element epilogue.
+    adk.quarter = (split == 1 && hs.chunks == 1) ? 1 : 0;
+    if (adk.quarter) grid.x = (unsigned)grid_x * 4;
+    if (bf16)
+      hipLaunchKernelGGL((mwgrad_het_adam_kernel<true>), grid, dim3(256),
+                         0, stream(), a, adk);
+    else
+      hipLaunchKernelGGL((mwgrad_het_adam_kernel<false>), grid, dim3(256),
+                         0, stream(), a, adk);
+  } else if (bf16)
     hipLaunchKernelGGL((mwgrad_het_kernel<true>), grid, dim3(256), 0,
                        stream(), a);
   else
@@ -1838,9 +2209,107 @@ void mwgrad_het(std::vector<torch::Tensor> dys,
                        stream(), a);
   if (split > 1) {
     int blocks = (int)std::min<int64_t>((poff + 255) / 256, 768);
-    hipLaunchKernelGGL(mwgrad_het_combine_kernel, dim3(blocks), dim3(256),
-                       0, stream(), a, split);
+    if (ad)
+      hipLaunchKernelGGL(mwgrad_het_combine_adam_kernel, dim3(blocks),
+                         dim3(256), 0, stream(), a, split, adk);
+    else
+      hipLaunchKernelGGL(mwgrad_het_combine_kernel, dim3(blocks),
+                         dim3(256), 0, stream(), a, split);
   }
+}
+
+void mwgrad_het(std::vector<torch::Tensor> dys,
+                std::vector<c10::optional<torch::Tensor>> ymasks,
+                std::vector<torch::Tensor> xs,
+                std::vector<torch::Tensor> dws,
+                std::vector<torch::Tensor> dbs,
+                std::vector<int64_t> Ms, std::vector<int64_t> Ns,
+                std::vector<int64_t> Ks, std::vector<int64_t> lddys,
+                std::vector<int64_t> ldxs, std::vector<int64_t> x_offs) {
+  mwgrad_het_impl(dys, ymasks, xs, dws, dbs, Ms, Ns, Ks, lddys, ldxs,
+                  x_offs, nullptr);
+}
+
+// True when the half-open element ranges [off, off+len) tile [0, n)
+// exactly once: no element uncovered, none covered twice.
+bool ranges_tile_exactly(std::vector<std::pair<int64_t, int64_t>> r,
+                         int64_t n) {
+  std::sort(r.begin(), r.end());
+  int64_t at = 0;
+  for (const auto& q : r) {
+    if (q.second <= 0) continue;
+    if (q.first != at) return false;
+    at += q.second;
+  }
+  return at == n;
+}
+
+// mwgrad_het + Adam (+polyak, +W^T refresh) in ONE launch: each tile
+// applies the update to the gradient it holds in registers.  Valid only
+// when nothing sits between the wgrad and Adam (single rank) and the
+// problems' dW/db slices tile the flat gradient buffer exactly once —
+// otherwise some parameter would miss (or double) its step, so raise.
+void mwgrad_het_adam(std::vector<torch::Tensor> dys,
+                     std::vector<c10::optional<torch::Tensor>> ymasks,
+                     std::vector<torch::Tensor> xs,
+                     std::vector<torch::Tensor> dws,
+                     std::vector<torch::Tensor> dbs,
+                     std::vector<int64_t> Ms, std::vector<int64_t> Ns,
+                     std::vector<int64_t> Ks, std::vector<int64_t> lddys,
+                     std::vector<int64_t> ldxs, std::vector<int64_t> x_offs,
+                     torch::Tensor p, torch::Tensor grad, torch::Tensor m,
+                     torch::Tensor v, torch::Tensor step, double lr,
+                     double b1, double b2, double eps, double wd,
+                     std::vector<c10::optional<torch::Tensor>> wts,
+                     c10::optional<torch::Tensor> targ, double rho) {
+  const int np = (int)dys.size();
+  TORCH_CHECK(np >= 1 && np <= MAXW, "mwgrad_het_adam: 1..12 problems");
+  TORCH_CHECK((int)wts.size() == np, "mwgrad_het_adam: one wt slot per "
+              "problem");
+  const int64_t n = grad.numel();
+  auto flat_ok = [&](const torch::Tensor& t) {
+    return t.is_contiguous() && t.scalar_type() == torch::kFloat32
+        && t.numel() == n;
+  };
+  TORCH_CHECK(flat_ok(p) && flat_ok(grad) && flat_ok(m) && flat_ok(v),
+              "mwgrad_het_adam: p/grad/m/v must be contiguous fp32 of one "
+              "size");
+  TORCH_CHECK(!targ.has_value() || flat_ok(*targ),
+              "mwgrad_het_adam: target size");
+  const float* gbase = grad.data_ptr<float>();
+  std::vector<std::pair<int64_t, int64_t>> ranges;
+  WAdam ad{};
+  for (int i = 0; i < np; ++i) {
+    const int64_t nk = Ns[i] * Ks[i];
+    TORCH_CHECK(dws[i].is_contiguous() && dws[i].numel() == nk,
+                "mwgrad_het_adam: dw ", i, " is not a contiguous [N,K]");
+    ranges.push_back({dws[i].data_ptr<float>() - gbase, nk});
+    if (dbs[i].numel()) {
+      TORCH_CHECK(dbs[i].is_contiguous() && dbs[i].numel() == Ns[i],
+                  "mwgrad_het_adam: db ", i);
+      ranges.push_back({dbs[i].data_ptr<float>() - gbase, Ns[i]});
+    }
+    ad.wt[i] = nullptr;
+    if (wts[i].has_value()) {
+      TORCH_CHECK(wts[i]->is_contiguous() && wts[i]->numel() == nk
+                  && wts[i]->scalar_type() == torch::kFloat32,
+                  "mwgrad_het_adam: wt ", i, " must be a contiguous [K,N]");
+      ad.wt[i] = wts[i]->data_ptr<float>();
+    }
+  }
+  TORCH_CHECK(ranges_tile_exactly(ranges, n),
+              "mwgrad_het_adam: the problems' dW/db slices do not tile the "
+              "flat gradient buffer exactly once");
+  ad.p = p.data_ptr<float>();
+  ad.m = m.data_ptr<float>();
+  ad.v = v.data_ptr<float>();
+  ad.targ = targ.has_value() ? targ->data_ptr<float>() : nullptr;
+  ad.grad = gbase;
+  ad.step = step.data_ptr<int64_t>();
+  ad.lr = (float)lr; ad.b1 = (float)b1; ad.b2 = (float)b2;
+  ad.eps = (float)eps; ad.wd = (float)wd; ad.rho = (float)rho;
+  mwgrad_het_impl(dys, ymasks, xs, dws, dbs, Ms, Ns, Ks, lddys, ldxs,
+                  x_offs, &ad);
 }
 
 void transpose_multi(std::vector<torch::Tensor> ws,
@@ -1872,7 +2341,7 @@ void gather2(torch::Tensor state, torch::Tensor act, torch::Tensor rew,
              torch::Tensor nstate, torch::Tensor done,
              torch::Tensor size_dev, torch::Tensor ctr, int64_t seed,
              torch::Tensor xc, torch::Tensor xc2, torch::Tensor orew,
-             torch::Tensor od, int64_t B) {
+             torch::Tensor od, int64_t B, int64_t ctr_add) {
   const int obs_dim = (int)state.size(1);
   const int act_dim = (int)act.size(1);
   int threads = std::min<int>(256, std::max(64, ((obs_dim + 63) / 64) * 64));
@@ -1880,7 +2349,7 @@ void gather2(torch::Tensor state, torch::Tensor act, torch::Tensor rew,
                      state.data_ptr<float>(), act.data_ptr<float>(),
                      rew.data_ptr<float>(), nstate.data_ptr<float>(),
                      done.data_ptr<float>(), size_dev.data_ptr<int64_t>(),
-                     ctr.data_ptr<int64_t>(), (uint64_t)seed,
+                     ctr.data_ptr<int64_t>(), ctr_add, (uint64_t)seed,
                      xc.data_ptr<float>(), xc2.data_ptr<float>(),
                      orew.data_ptr<float>(), od.data_ptr<float>(),
                      (int)B, obs_dim, act_dim, (int)xc.size(1));
@@ -1889,7 +2358,8 @@ void gather2(torch::Tensor state, torch::Tensor act, torch::Tensor rew,
 void tg_fwd2(torch::Tensor hl, torch::Tensor out0,
              int64_t col0, torch::Tensor out1, int64_t col1, int64_t B0,
              torch::Tensor logp, torch::Tensor prob, torch::Tensor ctr,
-             int64_t seed, double act_limit, double lo, double hi) {
+             int64_t seed, double act_limit, double lo, double hi,
+             int64_t ctr_add) {
   const int R = (int)hl.size(0), A = (int)hl.size(1) / 2;
   TORCH_CHECK(A <= 64);
   hipLaunchKernelGGL(tg_fwd2_kernel, dim3(R), dim3(64), 0, stream(),
@@ -1897,7 +2367,7 @@ void tg_fwd2(torch::Tensor hl, torch::Tensor out0,
                      out0.data_ptr<float>() + col0, (int)out0.size(1),
                      out1.data_ptr<float>() + col1, (int)out1.size(1),
                      (int)B0, logp.data_ptr<float>(), prob.data_ptr<float>(),
-                     ctr.data_ptr<int64_t>(), (uint64_t)seed, R, A,
+                     ctr.data_ptr<int64_t>(), ctr_add, (uint64_t)seed, R, A,
                      (float)act_limit, (float)lo, (float)hi);
 }
 
@@ -1926,9 +2396,15 @@ void qloss2(torch::Tensor q1, torch::Tensor q2, torch::Tensor q1t,
             c10::optional<torch::Tensor> wt3_0,
             c10::optional<torch::Tensor> wt3_1,
             c10::optional<torch::Tensor> dy2_0,
-            c10::optional<torch::Tensor> dy2_1, int64_t h2) {
+            c10::optional<torch::Tensor> dy2_1, int64_t h2,
+            c10::optional<torch::Tensor> bump0,
+            c10::optional<torch::Tensor> bump1,
+            c10::optional<torch::Tensor> bump2) {
   const bool fuse = dy2_0.has_value();
   TORCH_CHECK(!fuse || B <= LOSS_MAXB);
+  auto iptr = [](const c10::optional<torch::Tensor>& t) -> int64_t* {
+    return t.has_value() ? t->data_ptr<int64_t>() : nullptr;
+  };
   hipLaunchKernelGGL(qloss2_kernel, dim3(1), dim3(256), 0, stream(),
                      q1.data_ptr<float>(), q2.data_ptr<float>(),
                      q1t.data_ptr<float>(), q2t.data_ptr<float>(),
@@ -1939,7 +2415,8 @@ void qloss2(torch::Tensor q1, torch::Tensor q2, torch::Tensor q1t,
                      (float)gamma, (float)scale,
                      fptr(wt3_0), fptr(wt3_1),
                      fuse ? dy2_0->data_ptr<float>() : nullptr,
-                     fuse ? dy2_1->data_ptr<float>() : nullptr, (int)h2);
+                     fuse ? dy2_1->data_ptr<float>() : nullptr, (int)h2,
+                     iptr(bump0), iptr(bump1), iptr(bump2));
 }
 
 void piloss2(torch::Tensor q1, torch::Tensor q2, torch::Tensor logp,
@@ -2218,16 +2695,42 @@ void alpha_update(torch::Tensor log_alpha, torch::Tensor alpha_dev,
 void register_fused(pybind11::module_& m) {
   m.def("mgemm", &fused::mgemm,
         "multi-problem MFMA GEMM (fwd-form, strided, masked, sum2)");
+  m.def("mgemm_r1", &fused::mgemm_r1,
+        "masked GEMM whose A operand is a rank-1 product formed on read");
   m.def("mwgrad", &fused::mwgrad, "multi-problem wgrad + fused db");
   m.def("mwgrad_het", &fused::mwgrad_het,
         "heterogeneous multi-problem wgrad: one launch per phase");
+  m.def("mwgrad_het_adam", &fused::mwgrad_het_adam,
+        "heterogeneous wgrad with Adam (+polyak, +W^T) in the epilogue");
+  m.def("mwgrad_het_adam_split", &fused::mwgrad_het_adam_split,
+        "host-only: M slabs mwgrad_het_adam would use for these shapes");
+  m.def("ranges_tile_exactly", &fused::ranges_tile_exactly,
+        "host-only: do [off, off+len) ranges tile [0, n) exactly once");
   m.def("transpose_multi", &fused::transpose_multi,
         pybind11::arg("ws"), pybind11::arg("wts"),
         pybind11::arg("blocks") = std::vector<int64_t>{});
-  m.def("gather2", &fused::gather2);
-  m.def("tg_fwd2", &fused::tg_fwd2);
+  namespace py = pybind11;
+  // trailing ctr_add: the Philox key is ctr[0] + ctr_add, so a reader can
+  // run ahead of the launch that commits the bump (see qloss2's bump*)
+  m.def("gather2", &fused::gather2, py::arg("state"), py::arg("act"),
+        py::arg("rew"), py::arg("nstate"), py::arg("done"),
+        py::arg("size_dev"), py::arg("ctr"), py::arg("seed"), py::arg("xc"),
+        py::arg("xc2"), py::arg("orew"), py::arg("od"), py::arg("B"),
+        py::arg("ctr_add") = 0);
+  m.def("tg_fwd2", &fused::tg_fwd2, py::arg("hl"), py::arg("out0"),
+        py::arg("col0"), py::arg("out1"), py::arg("col1"), py::arg("B0"),
+        py::arg("logp"), py::arg("prob"), py::arg("ctr"), py::arg("seed"),
+        py::arg("act_limit"), py::arg("lo"), py::arg("hi"),
+        py::arg("ctr_add") = 0);
   m.def("tg_bwd2", &fused::tg_bwd2);
-  m.def("qloss2", &fused::qloss2);
+  m.def("qloss2", &fused::qloss2, py::arg("q1"), py::arg("q2"),
+        py::arg("q1t"), py::arg("q2t"), py::arg("logp_next"),
+        py::arg("rew"), py::arg("done"), py::arg("alpha_dev"),
+        py::arg("alpha_host"), py::arg("loss_acc"), py::arg("dq1"),
+        py::arg("dq2"), py::arg("B"), py::arg("gamma"), py::arg("scale"),
+        py::arg("wt3_0"), py::arg("wt3_1"), py::arg("dy2_0"),
+        py::arg("dy2_1"), py::arg("h2"), py::arg("bump0") = py::none(),
+        py::arg("bump1") = py::none(), py::arg("bump2") = py::none());
   m.def("piloss2", &fused::piloss2);
   m.def("alpha_update", &fused::alpha_update);
   m.def("tg_eps", &fused::tg_eps);
