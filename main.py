@@ -137,6 +137,10 @@ def parse_arguments() -> Namespace:
                         help="Welford online state normalization (wires in "
                              "the reference's dead sac/utils.py normalizer "
                              "— SURVEY.md Q9)")
+    parser.add_argument("--n-step", type=int, default=None,
+                        help="N-step returns in the Bellman backup "
+                             "(extension; default 1, or a resumed run's "
+                             "saved value; vector-observation envs only)")
     parser.add_argument("--eval-every", type=int, default=0,
                         help="Deterministic evaluation every N epochs "
                              "(extension; 0 = off)")
@@ -196,6 +200,7 @@ def main():
             epochs=1000, batch_size=64, steps_per_epoch=5000,
             start_steps=1000, update_after=1000, update_every=50,
             max_ep_len=5000, save_every=10,
+            n_step=1 if args.n_step is None else args.n_step,
         )
         if rank0 and args.logging:
             ckpt.log_params(params)
@@ -205,6 +210,10 @@ def main():
                              "eval_episodes": args.eval_episodes,
                              "eval_envs": args.eval_envs})
 
+    # a resumed run keeps its logged n_step (runs from before the flag
+    # existed have none and resume as 1-step) unless the flag overrides it
+    if args.run is not None and args.n_step is not None:
+        params["n_step"] = args.n_step
     if args.batch_size is not None:
         params["batch_size"] = args.batch_size
     if args.epochs is not None:

@@ -266,16 +266,21 @@ class WindowedStore:
         self.rew = np.zeros(window, dtype=np.float32)
         self.nobs = np.zeros((window, obs_dim), dtype=np.float32)
         self.done = np.zeros(window, dtype=np.float32)
+        # episode-boundary flags, staged only for an n-step buffer
+        self.end = np.zeros(window, dtype=np.float32) \
+            if getattr(buffer, "n_step", 1) > 1 else None
         self.n = 0
         self.window = window
 
-    def store(self, obs, act, rew, next_obs, done):
+    def store(self, obs, act, rew, next_obs, done, end=None):
         i = self.n
         self.obs[i] = obs
         self.act[i] = act
         self.rew[i] = rew
         self.nobs[i] = next_obs
         self.done[i] = done
+        if self.end is not None:
+            self.end[i] = done if end is None else end
         self.n += 1
         if self.n == self.window:
             self.flush()
@@ -284,8 +289,13 @@ class WindowedStore:
         if self.n == 0:
             return
         n = self.n
-        self.buffer.store_batch(self.obs[:n], self.act[:n], self.rew[:n],
-                                self.nobs[:n], self.done[:n])
+        if self.end is not None:
+            self.buffer.store_batch(self.obs[:n], self.act[:n], self.rew[:n],
+                                    self.nobs[:n], self.done[:n],
+                                    self.end[:n])
+        else:
+            self.buffer.store_batch(self.obs[:n], self.act[:n], self.rew[:n],
+                                    self.nobs[:n], self.done[:n])
         self.n = 0
 
 

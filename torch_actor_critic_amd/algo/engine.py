@@ -409,10 +409,27 @@ class FusedSACEngine:
             src_off = 0
             src_lda = k
 
+    def _gather(self, ctr_add: int):
+        """One-launch replay sample + gather into the concat buffers.  An
+        n-step buffer (ReplayBuffer.set_n_step) takes the n-step kernel:
+        same index draw and layout, rew/done carry the discounted reward
+        sum and the effective done, so the rest of the schedule — and
+        the launch count — is the same."""
+        ext, buf, B = self.ext, self.buffer, self.B
+        if buf.n_step > 1:
+            ext.gather2n(buf.state, buf.actions, buf.rewards,
+                         buf.next_state, buf.done, buf.episode_end,
+                         buf._size_dev, buf._ptr_dev, self.ctr, self.seed,
+                         buf.n_step, buf.gamma, self.XC, self.XC2, self.rew,
+                         self.done, B, ctr_add)
+        else:
+            ext.gather2(buf.state, buf.actions, buf.rewards, buf.next_state,
+                        buf.done, buf._size_dev, self.ctr, self.seed,
+                        self.XC, self.XC2, self.rew, self.done, B, ctr_add)
+
     def _phase_critic(self):
         ext = self.ext
         B, O, A, OC = self.B, self.O, self.A, self.OC
-        buf = self.buffer
         # the replay/noise counter AND both Adam step counters advance
         # once per update: either one launch up front, or (folded) the
         # readers key on ctr+1 and qloss2 commits all three — both Adam
@@ -422,9 +439,7 @@ class FusedSACEngine:
         if not fold:
             ext.bump3(self.ctr, self.q_opt.step_t, self.pi_opt.step_t)
         if self.sample:
-            ext.gather2(buf.state, buf.actions, buf.rewards, buf.next_state,
-                        buf.done, buf._size_dev, self.ctr, self.seed,
-                        self.XC, self.XC2, self.rew, self.done, B, ctr_add)
+            self._gather(ctr_add)
 
         # actor forward over stacked 2B rows of XC[:, :O]
         (wm, bm), (wl, bl) = self.head_w

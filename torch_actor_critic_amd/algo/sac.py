@@ -116,6 +116,7 @@ class SAC:
         eval_every: int = 0,
         eval_episodes: int = 10,
         eval_envs: int = 8,
+        n_step: int = 1,
     ):
         self.alpha = float(alpha)
         self.gamma = float(gamma)
@@ -131,6 +132,12 @@ class SAC:
         self.save_every = int(save_every)
         self.reference_pi_loss = reference_pi_loss
         self.use_graph = use_graph
+        # n-step returns (extension; 1 = the reference's 1-step backup).
+        # The replay buffer forms the n-step reward sum / next state /
+        # effective done at sampling time, the losses are unchanged
+        self.n_step = int(n_step)
+        if self.n_step < 1:
+            raise ValueError(f"n_step must be >= 1, got {n_step}")
 
         # optional learned entropy temperature (default off)
         self.learn_alpha = learn_alpha
@@ -384,6 +391,16 @@ class SAC:
                     for p in m.parameters():
                         comm.sync_flat_params(p.data)
 
+        # n-step returns: before the staging store below is built, which
+        # stages episode-boundary flags only for an n-step buffer
+        if self.n_step > 1:
+            if not hasattr(buffer, "set_n_step"):
+                raise ValueError(
+                    f"n_step={self.n_step} needs a replay buffer with "
+                    f"set_n_step(); {type(buffer).__name__} samples 1-step "
+                    "transitions only")
+            buffer.set_n_step(self.n_step, self.gamma)
+
         # per-rank seeding (reference algorithm.py:203-205)
         seed = 10000 * comm.proc_id()
         torch.manual_seed(seed)
@@ -455,7 +472,7 @@ class SAC:
             loss_pi_acc = torch.zeros((), device=device)
             n_updates = 0
 
-            for _ in range(self.steps_per_epoch):
+            for k in range(self.steps_per_epoch):
                 if (self.normalizer is not None
                         and not isinstance(state, MultiObservation)):
                     st = torch.as_tensor(np.asarray(state, dtype=np.float32))
@@ -493,6 +510,16 @@ class SAC:
                 thr.tick_env()
                 ep_len += 1
                 ep_ret += float(reward)
+                # n-step windows must not run into the next episode: the
+                # boundary is marked wherever the env is reset after this
+                # transition — termination, the max_ep_len truncation
+                # (stored with done=False) and the reset that closes
+                # every epoch
+                store_kw = {}
+                if self.n_step > 1:
+                    store_kw["end"] = float(
+                        bool(done) or ep_len == self.max_ep_len
+                        or k == self.steps_per_epoch - 1)
                 done = False if ep_len == self.max_ep_len else done
 
                 # store next_state normalized with the SAME statistics
@@ -509,10 +536,10 @@ class SAC:
                         self.normalizer.normalize_state(nst).numpy()
                 if wstore is not None:
                     wstore.store(state, action, float(reward), store_next,
-                                 float(done))
+                                 float(done), **store_kw)
                 else:
                     buffer.store(state, action, float(reward), store_next,
-                                 float(done))
+                                 float(done), **store_kw)
                 state = next_state
 
                 if done or ep_len == self.max_ep_len:

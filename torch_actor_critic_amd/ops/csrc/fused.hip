@@ -1335,6 +1335,96 @@ void gather2_kernel(const float* __restrict__ state,
   }
 }
 
+// N-step window walk — same code as tac_kernels.hip::nstep_walk (see the
+// comment there), duplicated to keep both translation units self-contained.
+// Run by ONE full wave; lane m < n loads slot (idx+m) % cap, a ballot finds
+// the first lane that closes the window, the discounted sum is added in
+// ascending m with contraction off.  All lanes return the same values.
+DEVINL int64_t nstep_walk_(const float* __restrict__ rew,
+                           const float* __restrict__ done,
+                           const float* __restrict__ ep_end, int64_t idx,
+                           int64_t cap, int64_t newest, int n, float gamma,
+                           float* R, float* deff) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x & 63;
+  const int64_t slot = (idx + lane) % cap;
+  float r = 0.f, d = 0.f;
+  bool stop = lane >= n - 1;
+  if (lane < n) {
+    r = rew[slot];
+    d = done[slot];
+    stop = stop || d != 0.f || ep_end[slot] != 0.f || slot == newest;
+  }
+  float disc = 1.f;
+  for (int m = 0; m < n - 1; ++m)
+    if (m < lane) disc *= gamma;
+  // lane n-1 always votes, so the mask is never empty
+  const unsigned long long mask = __ballot(stop);
+  const int last = __ffsll((long long)mask) - 1;
+  const float term = disc * r;
+  float acc = 0.f;
+  for (int m = 0; m <= last; ++m) acc += __shfl(term, m);
+  *R = acc;
+  const float de = 1.f - disc * (1.f - d);
+  *deff = __shfl(de, last);
+  return (idx + last) % cap;
+}
+
+// gather2 with n-step returns: same grid, index draw (key, counter,
+// ctr_add) and output layout as gather2_kernel; rew/done carry the
+// discounted n-step reward sum and the effective done, and XC rows B: hold
+// next_state of the window's LAST slot.  The loss kernels are unchanged:
+// gamma * (1 - done_eff) == gamma^M * (1 - done[last]).
+__global__ __launch_bounds__(256)
+void gather2n_kernel(const float* __restrict__ state,
+                     const float* __restrict__ act,
+                     const float* __restrict__ rew,
+                     const float* __restrict__ nstate,
+                     const float* __restrict__ done,
+                     const float* __restrict__ ep_end,
+                     const int64_t* __restrict__ size_dev,
+                     const int64_t* __restrict__ ptr_dev,
+                     const int64_t* __restrict__ ctr, int64_t ctr_add,
+                     uint64_t seed,
+                     float* __restrict__ xc,   // [2B, ldc]
+                     float* __restrict__ xc2,  // [B, ldc]
+                     float* __restrict__ orew, float* __restrict__ od,
+                     int B, int obs_dim, int act_dim, int ldc,
+                     int64_t cap, int n, float gamma) {
+  __shared__ int64_t s_last;
+  const int j = blockIdx.x;
+  const uint64_t size = (uint64_t)size_dev[0];
+  P4 r = philox_(seed, (uint64_t)(ctr[0] + ctr_add), (uint64_t)j);
+  uint64_t u = ((uint64_t)r.x << 32) | r.y;
+  int64_t idx = (int64_t)(u % (size ? size : 1));
+
+  if (threadIdx.x < 64) {
+    // size == 0: slot 0 counts as the newest, nothing past it is consumed
+    const int64_t newest = size ? (ptr_dev[0] + cap - 1) % cap : 0;
+    float R, de;
+    const int64_t last = nstep_walk_(rew, done, ep_end, idx, cap, newest, n,
+                                     gamma, &R, &de);
+    if (threadIdx.x == 0) {
+      s_last = last;
+      orew[j] = R;
+      od[j] = de;
+    }
+  }
+  const float* srow = state + idx * obs_dim;
+  const float* arow = act + idx * act_dim;
+  for (int c = threadIdx.x; c < obs_dim; c += blockDim.x) {
+    float s = srow[c];
+    xc[(int64_t)j * ldc + c] = s;           // s -> XC rows :B
+    xc2[(int64_t)j * ldc + c] = s;          // s -> XC2
+  }
+  for (int c = threadIdx.x; c < act_dim; c += blockDim.x)
+    xc[(int64_t)j * ldc + obs_dim + c] = arow[c];  // a -> XC rows :B
+  __syncthreads();
+  const float* nrow = nstate + s_last * obs_dim;
+  for (int c = threadIdx.x; c < obs_dim; c += blockDim.x)
+    xc[(int64_t)(B + j) * ldc + c] = nrow[c];  // ns[last] -> XC rows B:
+}
+
 // ---------------------------------------------------------------------------
 // Fused tanh-Gaussian head, stacked rows with split outputs + internal
 // Philox noise (row < B0 -> out0 slice; else out1 slice)
@@ -2355,6 +2445,48 @@ void gather2(torch::Tensor state, torch::Tensor act, torch::Tensor rew,
                      (int)B, obs_dim, act_dim, (int)xc.size(1));
 }
 
+void gather2n(torch::Tensor state, torch::Tensor act, torch::Tensor rew,
+              torch::Tensor nstate, torch::Tensor done, torch::Tensor ep_end,
+              torch::Tensor size_dev, torch::Tensor ptr_dev,
+              torch::Tensor ctr, int64_t seed, int64_t n, double gamma,
+              torch::Tensor xc, torch::Tensor xc2, torch::Tensor orew,
+              torch::Tensor od, int64_t B, int64_t ctr_add) {
+  const int obs_dim = (int)state.size(1);
+  const int act_dim = (int)act.size(1);
+  const int64_t cap = state.size(0);
+  TORCH_CHECK(n >= 1 && n <= 64, "n_step must be in 1..64");
+  for (const torch::Tensor& t : {state, act, rew, nstate, done, ep_end, xc,
+                                 xc2, orew, od})
+    TORCH_CHECK(t.is_cuda() && t.is_contiguous() &&
+                t.dtype() == torch::kFloat32,
+                "gather2n: tensors must be contiguous fp32 device tensors");
+  TORCH_CHECK(cap >= 1 && rew.numel() == cap && done.numel() == cap &&
+              ep_end.numel() == cap && nstate.size(0) == cap &&
+              nstate.size(1) == obs_dim && act.size(0) == cap,
+              "gather2n: ring fields must share one capacity");
+  TORCH_CHECK(ptr_dev.is_cuda() && ptr_dev.dtype() == torch::kInt64 &&
+              ptr_dev.numel() == 1 && size_dev.is_cuda() &&
+              size_dev.dtype() == torch::kInt64 && size_dev.numel() == 1,
+              "gather2n: size_dev / ptr_dev must be int64 [1] device tensors");
+  TORCH_CHECK(B >= 1 && xc.size(0) >= 2 * B && xc2.size(0) >= B &&
+              xc.size(1) >= obs_dim + act_dim && xc2.size(1) == xc.size(1) &&
+              orew.numel() >= B && od.numel() >= B,
+              "gather2n: batch buffers too small");
+  int threads = std::min<int>(256, std::max(64, ((obs_dim + 63) / 64) * 64));
+  hipLaunchKernelGGL(gather2n_kernel, dim3((int)B), dim3(threads), 0,
+                     stream(),
+                     state.data_ptr<float>(), act.data_ptr<float>(),
+                     rew.data_ptr<float>(), nstate.data_ptr<float>(),
+                     done.data_ptr<float>(), ep_end.data_ptr<float>(),
+                     size_dev.data_ptr<int64_t>(),
+                     ptr_dev.data_ptr<int64_t>(),
+                     ctr.data_ptr<int64_t>(), ctr_add, (uint64_t)seed,
+                     xc.data_ptr<float>(), xc2.data_ptr<float>(),
+                     orew.data_ptr<float>(), od.data_ptr<float>(),
+                     (int)B, obs_dim, act_dim, (int)xc.size(1), cap, (int)n,
+                     (float)gamma);
+}
+
 void tg_fwd2(torch::Tensor hl, torch::Tensor out0,
              int64_t col0, torch::Tensor out1, int64_t col1, int64_t B0,
              torch::Tensor logp, torch::Tensor prob, torch::Tensor ctr,
@@ -2717,6 +2849,12 @@ void register_fused(pybind11::module_& m) {
         py::arg("size_dev"), py::arg("ctr"), py::arg("seed"), py::arg("xc"),
         py::arg("xc2"), py::arg("orew"), py::arg("od"), py::arg("B"),
         py::arg("ctr_add") = 0);
+  m.def("gather2n", &fused::gather2n, py::arg("state"), py::arg("act"),
+        py::arg("rew"), py::arg("nstate"), py::arg("done"),
+        py::arg("ep_end"), py::arg("size_dev"), py::arg("ptr_dev"),
+        py::arg("ctr"), py::arg("seed"), py::arg("n"), py::arg("gamma"),
+        py::arg("xc"), py::arg("xc2"), py::arg("orew"), py::arg("od"),
+        py::arg("B"), py::arg("ctr_add") = 0);
   m.def("tg_fwd2", &fused::tg_fwd2, py::arg("hl"), py::arg("out0"),
         py::arg("col0"), py::arg("out1"), py::arg("col1"), py::arg("B0"),
         py::arg("logp"), py::arg("prob"), py::arg("ctr"), py::arg("seed"),

@@ -720,6 +720,103 @@ void replay_gather_kernel(const float* __restrict__ state,
 }
 
 // ---------------------------------------------------------------------------
+// N-step replay sample + gather (buffer/replay.py::sample_at is the
+// executable definition of the window semantics)
+// ---------------------------------------------------------------------------
+
+// N-step window walk for one sampled slot, run by ONE full wave (all 64
+// lanes active, n <= 64).  Lane m < n loads (rew, done, episode_end) of
+// slot (idx+m) % cap and forms its own gamma^m by repeated multiply; a
+// wave64 ballot finds the first lane whose slot closes the window
+// (terminal, episode boundary, newest slot, or m == n-1), so the n slots
+// cost one global-load latency instead of a chain of n dependent loads.
+// R = sum_{m<M} gamma^m rew[m] is added in ascending m (the reference
+// order), deff = 1 - gamma^(M-1) * (1 - done[last]); contraction is off so
+// every product is rounded before it is added, as in the reference.
+// Returns the last slot of the window; all lanes get the same values.
+DEVINL int64_t nstep_walk(const float* __restrict__ rew,
+                          const float* __restrict__ done,
+                          const float* __restrict__ ep_end, int64_t idx,
+                          int64_t cap, int64_t newest, int n, float gamma,
+                          float* R, float* deff) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int64_t slot = (idx + lane) % cap;
+  float r = 0.f, d = 0.f;
+  bool stop = lane >= n - 1;
+  if (lane < n) {
+    r = rew[slot];
+    d = done[slot];
+    stop = stop || d != 0.f || ep_end[slot] != 0.f || slot == newest;
+  }
+  float disc = 1.f;
+  for (int m = 0; m < n - 1; ++m)
+    if (m < lane) disc *= gamma;
+  // lane n-1 always votes, so the mask is never empty
+  const unsigned long long mask = __ballot(stop);
+  const int last = __ffsll((long long)mask) - 1;
+  const float term = disc * r;
+  float acc = 0.f;
+  for (int m = 0; m <= last; ++m) acc += __shfl(term, m);
+  *R = acc;
+  const float de = 1.f - disc * (1.f - d);
+  *deff = __shfl(de, last);
+  return (idx + last) % cap;
+}
+
+// Same grid and index draw as replay_gather_kernel (same key, counter and
+// block -> row map, so for one counter value both pick the same slots).
+// Wave 0 walks the window and hands the last slot to the block through
+// LDS; state/action rows are copied from slot idx, next_state from the
+// last slot.  cap is the ring capacity; with size == 0 slot 0 counts as
+// the newest slot, so nothing beyond it is consumed.
+__global__ __launch_bounds__(256)
+void replay_gather_n_kernel(const float* __restrict__ state,
+                            const float* __restrict__ act,
+                            const float* __restrict__ rew,
+                            const float* __restrict__ nstate,
+                            const float* __restrict__ done,
+                            const float* __restrict__ ep_end,
+                            const int64_t* __restrict__ size_dev,
+                            const int64_t* __restrict__ ptr_dev,
+                            const int64_t* __restrict__ ctr,
+                            uint64_t seed,
+                            float* __restrict__ os, float* __restrict__ oa,
+                            float* __restrict__ orew, float* __restrict__ ons,
+                            float* __restrict__ od,
+                            int obs_dim, int act_dim, int64_t cap, int n,
+                            float gamma) {
+  __shared__ int64_t s_last;
+  const int j = blockIdx.x;
+  const uint64_t size = (uint64_t)size_dev[0];
+  Philox4 r = philox4(seed, (uint64_t)ctr[0], (uint64_t)j);
+  uint64_t u = ((uint64_t)r.x << 32) | r.y;
+  int64_t idx = (int64_t)(u % (size ? size : 1));
+
+  if (threadIdx.x < WAVE) {
+    const int64_t newest = size ? (ptr_dev[0] + cap - 1) % cap : 0;
+    float R, de;
+    const int64_t last = nstep_walk(rew, done, ep_end, idx, cap, newest, n,
+                                    gamma, &R, &de);
+    if (threadIdx.x == 0) {
+      s_last = last;
+      orew[j] = R;
+      od[j] = de;
+    }
+  }
+  const float* srow = state + (int64_t)idx * obs_dim;
+  float* osr = os + (int64_t)j * obs_dim;
+  for (int c = threadIdx.x; c < obs_dim; c += blockDim.x) osr[c] = srow[c];
+  const float* arow = act + (int64_t)idx * act_dim;
+  float* oar = oa + (int64_t)j * act_dim;
+  for (int c = threadIdx.x; c < act_dim; c += blockDim.x) oar[c] = arow[c];
+  __syncthreads();
+  const float* nrow = nstate + s_last * obs_dim;
+  float* onr = ons + (int64_t)j * obs_dim;
+  for (int c = threadIdx.x; c < obs_dim; c += blockDim.x) onr[c] = nrow[c];
+}
+
+// ---------------------------------------------------------------------------
 // Visual replay gather: ONE kernel draws the Philox index and copies
 // features / frames (with u8 -> f32 dequantization) / actions / rewards
 // / done into the static batch — replaces ~18 aten index/copy/decode
@@ -1057,6 +1154,53 @@ void replay_sample_into(torch::Tensor state, torch::Tensor act,
                      od.data_ptr<float>(), obs_dim, act_dim);
 }
 
+// n-step variant (n > 1): ep_end is the ring's episode-boundary field and
+// ptr_dev the device mirror of the write head; both are read at run time,
+// so a captured launch sees transitions stored after capture.
+void replay_sample_into_n(torch::Tensor state, torch::Tensor act,
+                          torch::Tensor rew, torch::Tensor nstate,
+                          torch::Tensor done, torch::Tensor ep_end,
+                          torch::Tensor size_dev, torch::Tensor ptr_dev,
+                          torch::Tensor ctr, int64_t seed, int64_t n,
+                          double gamma,
+                          torch::Tensor os, torch::Tensor oa,
+                          torch::Tensor orew, torch::Tensor ons,
+                          torch::Tensor od) {
+  CHECK_IN(state); CHECK_IN(act); CHECK_IN(rew); CHECK_IN(nstate);
+  CHECK_IN(done); CHECK_IN(ep_end);
+  CHECK_IN(os); CHECK_IN(oa); CHECK_IN(orew); CHECK_IN(ons); CHECK_IN(od);
+  TORCH_CHECK(n >= 1 && n <= 64, "n_step must be in 1..64");
+  const int64_t cap = state.size(0);
+  TORCH_CHECK(cap >= 1 && rew.numel() == cap && done.numel() == cap &&
+              ep_end.numel() == cap && nstate.size(0) == cap &&
+              act.size(0) == cap, "ring fields must share one capacity");
+  TORCH_CHECK(ptr_dev.is_cuda() && ptr_dev.dtype() == torch::kInt64 &&
+              ptr_dev.numel() == 1 && size_dev.is_cuda() &&
+              size_dev.dtype() == torch::kInt64 && size_dev.numel() == 1,
+              "size_dev / ptr_dev must be int64 [1] device tensors");
+  const int B = os.size(0);
+  const int obs_dim = state.size(1);
+  const int act_dim = act.size(1);
+  TORCH_CHECK(os.size(1) == obs_dim && ons.size(1) == obs_dim &&
+              ons.size(0) == B && oa.size(0) == B && oa.size(1) == act_dim &&
+              orew.numel() == B && od.numel() == B, "batch shape mismatch");
+  auto s = cur_stream();
+  hipLaunchKernelGGL(bump_counter_kernel, dim3(1), dim3(1), 0, s,
+                     ctr.data_ptr<int64_t>());
+  int threads = std::min(256, std::max(64, ((obs_dim + 63) / 64) * 64));
+  hipLaunchKernelGGL(replay_gather_n_kernel, dim3(B), dim3(threads), 0, s,
+                     state.data_ptr<float>(), act.data_ptr<float>(),
+                     rew.data_ptr<float>(), nstate.data_ptr<float>(),
+                     done.data_ptr<float>(), ep_end.data_ptr<float>(),
+                     size_dev.data_ptr<int64_t>(),
+                     ptr_dev.data_ptr<int64_t>(),
+                     ctr.data_ptr<int64_t>(), (uint64_t)seed,
+                     os.data_ptr<float>(), oa.data_ptr<float>(),
+                     orew.data_ptr<float>(), ons.data_ptr<float>(),
+                     od.data_ptr<float>(), obs_dim, act_dim, cap, (int)n,
+                     (float)gamma);
+}
+
 // One-kernel visual ring store: quantize both fp32 frames to u8 and
 // write every field of the transition at ring slot `idx` — replaces the
 // CPU-side encode chain + ~10 aten copies per env step.
@@ -1225,6 +1369,21 @@ std::vector<torch::Tensor> replay_sample(torch::Tensor state, torch::Tensor act,
   return {os, oa, orew, ons, od};
 }
 
+std::vector<torch::Tensor> replay_sample_n(
+    torch::Tensor state, torch::Tensor act, torch::Tensor rew,
+    torch::Tensor nstate, torch::Tensor done, torch::Tensor ep_end,
+    torch::Tensor size_dev, torch::Tensor ptr_dev, torch::Tensor ctr,
+    int64_t seed, int64_t n, double gamma, int64_t batch) {
+  auto os = torch::empty({batch, state.size(1)}, state.options());
+  auto oa = torch::empty({batch, act.size(1)}, state.options());
+  auto orew = torch::empty({batch}, state.options());
+  auto ons = torch::empty({batch, state.size(1)}, state.options());
+  auto od = torch::empty({batch}, state.options());
+  replay_sample_into_n(state, act, rew, nstate, done, ep_end, size_dev,
+                       ptr_dev, ctr, seed, n, gamma, os, oa, orew, ons, od);
+  return {os, oa, orew, ons, od};
+}
+
 }  // namespace
 
 // shared compute-mode flag for the fused-engine / conv TUs
@@ -1255,6 +1414,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adam_step_", &adam_step_);
   m.def("replay_sample", &replay_sample);
   m.def("replay_sample_into", &replay_sample_into);
+  m.def("replay_sample_n", &replay_sample_n);
+  m.def("replay_sample_into_n", &replay_sample_into_n);
   m.def("visual_sample_into", &visual_sample_into);
   m.def("visual_store_into", &visual_store_into);
   m.def("philox_randn_", &philox_randn_);
