@@ -141,6 +141,15 @@ def parse_arguments() -> Namespace:
                         help="N-step returns in the Bellman backup "
                              "(extension; default 1, or a resumed run's "
                              "saved value; vector-observation envs only)")
+    parser.add_argument("--per", action="store_true", default=None,
+                        help="Prioritized experience replay (extension; "
+                             "default off, or a resumed run's saved value; "
+                             "vector-observation envs only)")
+    parser.add_argument("--per-alpha", type=float, default=None,
+                        help="Priority exponent (default 0.6)")
+    parser.add_argument("--per-beta", type=float, default=None,
+                        help="Initial importance-weight exponent, annealed "
+                             "to 1 over the run (default 0.4)")
     parser.add_argument("--eval-every", type=int, default=0,
                         help="Deterministic evaluation every N epochs "
                              "(extension; 0 = off)")
@@ -201,6 +210,9 @@ def main():
             start_steps=1000, update_after=1000, update_every=50,
             max_ep_len=5000, save_every=10,
             n_step=1 if args.n_step is None else args.n_step,
+            per=int(bool(args.per)),
+            per_alpha=0.6 if args.per_alpha is None else args.per_alpha,
+            per_beta=0.4 if args.per_beta is None else args.per_beta,
         )
         if rank0 and args.logging:
             ckpt.log_params(params)
@@ -214,6 +226,12 @@ def main():
     # existed have none and resume as 1-step) unless the flag overrides it
     if args.run is not None and args.n_step is not None:
         params["n_step"] = args.n_step
+    # likewise the prioritized-replay settings
+    if args.run is not None:
+        for key, val in (("per", args.per), ("per_alpha", args.per_alpha),
+                         ("per_beta", args.per_beta)):
+            if val is not None:
+                params[key] = int(val) if key == "per" else val
     if args.batch_size is not None:
         params["batch_size"] = args.batch_size
     if args.epochs is not None:

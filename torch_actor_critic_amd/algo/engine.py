@@ -22,6 +22,11 @@ from the multi-problem MFMA kernels in ops/csrc/fused.hip:
  * the pi-phase K=1 dgrad of the critic's last layer is never
    materialised: the next dgrad GEMM forms dqp (x) w_last in registers
    while staging (TAC_AMD_R1_DGRAD=0 restores the K=1 launch);
+ * with a prioritized buffer (ReplayBuffer.set_prioritized) the gather
+   draws from the ring's sum tree (gather2p), qloss2 runs its
+   importance-weighted instantiation and exports the TD errors, and one
+   more launch (per_update) writes the new priorities — the default
+   launch count plus one; the default schedule is untouched;
  * the replay gather writes states/actions/next-states directly into
    concat-layout buffers (XC = [s|a ; ns|a2], XC2 = [s|pi]) — torch.cat
    never appears;
@@ -105,6 +110,14 @@ class FusedSACEngine:
         self.rew = torch.zeros(B, **f32)
         self.done = torch.zeros(B, **f32)
         self.ctr = torch.zeros(1, dtype=torch.int64, device=device)
+        # prioritized replay (ReplayBuffer.set_prioritized): the drawn
+        # slots, their probabilities and the TD errors qloss2 exports for
+        # the priority update — one launch more than the default schedule
+        self.per = bool(getattr(buffer, "prioritized", False)) and sample
+        if self.per:
+            self.idx = torch.zeros(B, dtype=torch.int64, device=device)
+            self.pprob = torch.zeros(B, **f32)
+            self.td = torch.zeros(B, **f32)
 
         # actor trunk
         self.a_hidden = [l.out_features for l in actor.layers]
@@ -414,9 +427,22 @@ class FusedSACEngine:
         n-step buffer (ReplayBuffer.set_n_step) takes the n-step kernel:
         same index draw and layout, rew/done carry the discounted reward
         sum and the effective done, so the rest of the schedule — and
-        the launch count — is the same."""
+        the launch count — is the same.  A prioritized buffer takes
+        gather2p (either n)."""
         ext, buf, B = self.ext, self.buffer, self.B
-        if buf.n_step > 1:
+        if self.per:
+            # stratified draw from the sum tree, same Philox keying; the
+            # n-step fields are placeholders while n_step == 1
+            nstep = buf.n_step > 1
+            ext.gather2p(buf.state, buf.actions, buf.rewards,
+                         buf.next_state, buf.done,
+                         buf.episode_end if nstep else buf.done,
+                         buf._size_dev,
+                         buf._ptr_dev if nstep else buf._size_dev,
+                         buf._per_tree, self.ctr, self.seed, buf.n_step,
+                         buf.gamma, self.XC, self.XC2, self.rew, self.done,
+                         self.idx, self.pprob, None, B, ctr_add)
+        elif buf.n_step > 1:
             ext.gather2n(buf.state, buf.actions, buf.rewards,
                          buf.next_state, buf.done, buf.episode_end,
                          buf._size_dev, buf._ptr_dev, self.ctr, self.seed,
@@ -509,6 +535,11 @@ class FusedSACEngine:
         fuse = self._loss_fuse
         bump = ((self.ctr, self.q_opt.step_t, self.pi_opt.step_t)
                 if self._bump_fold else (None, None, None))
+        # importance-weighted instantiation for a prioritized buffer; beta
+        # is a device scalar, so a captured graph sees its annealing
+        buf = self.buffer
+        per = ((self.pprob, buf._size_dev, buf._beta_dev, self.td)
+               if self.per else ())
         ext.qloss2(q[0], q[1], qt[0], qt[1], self.logp[B:], self.rew,
                    self.done, self.alpha_dev, self.alpha_host,
                    self.loss_q_acc, self.dq[0], self.dq[1], B,
@@ -517,7 +548,12 @@ class FusedSACEngine:
                    self.cwt[1][nL - 1] if fuse else None,
                    self.dc[0][nL - 2] if fuse else None,
                    self.dc[1][nL - 2] if fuse else None,
-                   self.c_w[nL - 2] if fuse else 0, *bump)
+                   self.c_w[nL - 2] if fuse else 0, *bump, *per)
+        if self.per:
+            # new priorities from this batch's TD errors, ahead of
+            # everything that can precede the next gather
+            ext.per_update(buf._per_tree, buf.max_size, self.idx, self.td,
+                           buf.per_alpha, buf.per_eps, buf._max_priority)
 
         # critic backward (wgrad into flat grads; dgrad via cached W^T)
         d = self.dq

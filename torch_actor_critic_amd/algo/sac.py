@@ -66,14 +66,24 @@ def eval_pi_loss(actor, critic, state, next_state, alpha,
 
 
 def eval_q_loss(actor, critic, target_critic, states, actions, rewards,
-                next_states, done, alpha, gamma, reward_scale):
-    """Twin-Q Bellman MSE (reference algorithm.py:46-74)."""
+                next_states, done, alpha, gamma, reward_scale, weights=None,
+                return_td=False):
+    """Twin-Q Bellman MSE (reference algorithm.py:46-74).  ``weights``
+    (prioritized replay) scale each row's squared errors; ``return_td``
+    also returns the rows' absolute TD errors (|e1| + |e2|) / 2."""
     with torch.no_grad():
         a2, logp_ac = actor(next_states)
         q1_t, q2_t = target_critic(next_states, a2)
     q1, q2 = critic(states, actions)
-    return Fo.sac_q_loss(q1, q2, q1_t, q2_t, logp_ac, rewards, done,
-                         alpha, gamma, reward_scale)
+    loss = Fo.sac_q_loss(q1, q2, q1_t, q2_t, logp_ac, rewards, done,
+                         alpha, gamma, reward_scale, weights=weights)
+    if not return_td:
+        return loss
+    with torch.no_grad():
+        backup = reward_scale * rewards + gamma * (1.0 - done) * (
+            torch.min(q1_t, q2_t) - alpha * logp_ac)
+        td = 0.5 * ((q1 - backup).abs() + (q2 - backup).abs())
+    return loss, td
 
 
 def update_targets(source: nn.Module, target: nn.Module, polyak: float):
@@ -117,6 +127,10 @@ class SAC:
         eval_episodes: int = 10,
         eval_envs: int = 8,
         n_step: int = 1,
+        per: bool = False,
+        per_alpha: float = 0.6,
+        per_beta: float = 0.4,
+        per_eps: float = 1e-6,
     ):
         self.alpha = float(alpha)
         self.gamma = float(gamma)
@@ -138,6 +152,15 @@ class SAC:
         self.n_step = int(n_step)
         if self.n_step < 1:
             raise ValueError(f"n_step must be >= 1, got {n_step}")
+
+        # prioritized replay (extension; default off): the buffer samples
+        # proportionally to (|td| + per_eps)^per_alpha, the critic loss is
+        # importance-weighted with an exponent annealed from per_beta to
+        # 1 over the run; the policy loss is not weighted
+        self.per = bool(per)
+        self.per_alpha = float(per_alpha)
+        self.per_beta = float(per_beta)
+        self.per_eps = float(per_eps)
 
         # optional learned entropy temperature (default off)
         self.learn_alpha = learn_alpha
@@ -176,12 +199,22 @@ class SAC:
         return self.alpha
 
     def update_critic(self, q_opt, actor, critic, target_critic,
-                      samples: Batch):
+                      samples: Batch, buffer=None):
+        """``buffer``: with a prioritized batch, where the new priorities
+        of its slots are written."""
         q_opt.zero_grad()
+        # only a prioritized ReplayBuffer batch carries weights
+        weights = getattr(samples, "weights", None)
+        weighted = weights is not None
         loss_q = eval_q_loss(
             actor, critic, target_critic, samples.states, samples.actions,
             samples.rewards, samples.next_states, samples.done,
-            self._alpha_value(), self.gamma, self.reward_scale)
+            self._alpha_value(), self.gamma, self.reward_scale,
+            weights=weights, return_td=weighted)
+        if weighted:
+            loss_q, td = loss_q
+            if buffer is not None:
+                buffer.update_priorities(samples.indices, td)
         loss_q.backward()
         self._allreduce(critic, self._critic_fp)
         q_opt.step()
@@ -257,6 +290,13 @@ class SAC:
                 logger.warning("fused engine capture failed (%r); trying "
                                "autograd graph", e)
         if self.learn_alpha:
+            self._graph_failed = True
+            return None
+        if getattr(buffer, "prioritized", False):
+            # the autograd-captured update knows neither the weights nor
+            # the priority update: training with it would be silently wrong
+            logger.info("prioritized replay: no captured update for this "
+                        "model/buffer, using eager updates")
             self._graph_failed = True
             return None
         try:
@@ -400,6 +440,14 @@ class SAC:
                     f"set_n_step(); {type(buffer).__name__} samples 1-step "
                     "transitions only")
             buffer.set_n_step(self.n_step, self.gamma)
+        # prioritized replay: likewise before the first store
+        if self.per:
+            if not hasattr(buffer, "set_prioritized"):
+                raise ValueError(
+                    "per=True needs a replay buffer with set_prioritized(); "
+                    f"{type(buffer).__name__} samples uniformly only")
+            if not getattr(buffer, "prioritized", False):
+                buffer.set_prioritized(self.per_alpha, self.per_eps)
 
         # per-rank seeding (reference algorithm.py:203-205)
         seed = 10000 * comm.proc_id()
@@ -463,8 +511,16 @@ class SAC:
         step = 0
         ep_ret, ep_len = 0.0, 0
         _tried_visual_act = False
+        first_epoch = None
         for e in pbar:
             self._last_epoch = e
+            if self.per:
+                # importance exponent: per_beta -> 1.0 at the last epoch
+                first_epoch = e if first_epoch is None else first_epoch
+                frac = ((e - first_epoch) / (self.epochs - 1)
+                        if self.epochs > 1 else 1.0)
+                buffer.set_beta(
+                    self.per_beta + (1.0 - self.per_beta) * min(frac, 1.0))
             episode_rewards: t.List[float] = []
             episode_lengths: t.List[float] = []
             # device-side loss accumulators — no per-update host sync
@@ -567,7 +623,8 @@ class SAC:
                         for _u in range(self.update_every):
                             samples = buffer.sample(self.batch_size)
                             loss_q = self.update_critic(
-                                q_opt, actor, critic, target_critic, samples)
+                                q_opt, actor, critic, target_critic, samples,
+                                **({"buffer": buffer} if self.per else {}))
                             loss_pi = self.update_policy(
                                 pi_opt, actor, critic, samples)
                             self.update_targets_fast(critic)

@@ -22,6 +22,12 @@ but designed for MI355X:
   reward sum, the next state n steps later and an *effective* done, so
   the unchanged 1-step loss kernels compute the n-step Bellman target
   (``sample_at`` is the executable definition).
+* Optional prioritized replay (extension, default off): after
+  ``set_prioritized(alpha, eps)`` the ring carries a fan-out-64 sum tree
+  of fp32 priorities in HBM; samplers draw stratified from it and return
+  the drawn slots and importance weights, ``update_priorities`` writes
+  ``(|td| + eps)^alpha`` back (``draw`` / ``_update_priorities_ref`` are
+  the executable definitions).
 """
 
 import typing as t
@@ -43,6 +49,40 @@ class Batch:
     rewards: torch.Tensor
     next_states: torch.Tensor
     done: torch.Tensor
+    # prioritized replay only (None otherwise): the ring slots drawn and
+    # the importance weights (size * prob)^-beta / max_j of the same
+    indices: t.Optional[torch.Tensor] = None
+    weights: t.Optional[torch.Tensor] = None
+
+
+PER_FAN = 64    # sum-tree fan-out: one wave64 loads all children of a node
+
+
+def per_layout(cap: int) -> t.Tuple[int, t.List[int], t.List[int], int]:
+    """(L, nodes per level, offset of each padded level, total floats) of
+    the sum tree over ``cap`` leaves: level L is the leaves, level k node i
+    sums level k+1 nodes 64i..64i+63, every level is zero-padded to a
+    multiple of 64 and the levels are stored root first."""
+    L = 1
+    while PER_FAN ** L < cap:
+        L += 1
+    ns = [cap]
+    for _ in range(L):
+        ns.insert(0, -(-ns[0] // PER_FAN))
+    offs, total = [], 0
+    for n in ns:
+        offs.append(total)
+        total += -(-n // PER_FAN) * PER_FAN
+    return L, ns, offs, total
+
+
+def per_node_sum(c: torch.Tensor) -> torch.Tensor:
+    """Sum of the 64 children ``c[..., :64]`` in the fixed halving order —
+    what a ``__shfl_down`` reduction leaves in lane 0."""
+    v = c
+    for s in (32, 16, 8, 4, 2, 1):
+        v = v[..., :s] + v[..., s:2 * s]
+    return v[..., 0]
 
 
 class ReplayBuffer:
@@ -77,6 +117,17 @@ class ReplayBuffer:
         self.gamma = 1.0
         self.episode_end: t.Optional[torch.Tensor] = None
         self._ptr_dev: t.Optional[torch.Tensor] = None
+        # prioritized replay (set_prioritized): off by default — nothing
+        # below is allocated, copied or launched while it is off
+        self.prioritized = False
+        self.per_alpha = 0.0
+        self.per_eps = 0.0
+        self._per_tree: t.Optional[torch.Tensor] = None
+        self._per_pad: t.List[torch.Tensor] = []
+        self._per_n: t.List[int] = []
+        self._per_L = 0
+        self._max_priority: t.Optional[torch.Tensor] = None
+        self._beta_dev: t.Optional[torch.Tensor] = None
 
     MAX_N_STEP = 64   # one wave64 lane per window slot in the gather kernels
 
@@ -104,6 +155,151 @@ class ReplayBuffer:
         self.n_step = n
         self.gamma = float(gamma)
 
+    # -- prioritized replay ---------------------------------------------
+
+    def set_prioritized(self, alpha: float = 0.6, eps: float = 1e-6) -> None:
+        """Sample proportionally to ``(|td| + eps)^alpha`` from now on.
+        Allocates the sum tree (see ``per_layout``), so the buffer must
+        still be empty: slots never written have priority 0 and are never
+        drawn."""
+        if self.size != 0:
+            raise ValueError(
+                "set_prioritized needs an empty buffer: transitions stored "
+                "so far carry no priority")
+        if not alpha >= 0.0 or not eps > 0.0:
+            raise ValueError(
+                f"need alpha >= 0 and eps > 0, got {alpha}, {eps}")
+        L, ns, offs, total = per_layout(self.max_size)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        self._per_tree = torch.zeros(total, **f32)
+        self._per_L, self._per_n = L, ns
+        self._per_pad = [
+            self._per_tree[o:o + -(-n // PER_FAN) * PER_FAN]
+            for o, n in zip(offs, ns)]
+        self._max_priority = torch.ones(1, **f32)
+        self._beta_dev = torch.ones(1, **f32)
+        self.per_alpha, self.per_eps = float(alpha), float(eps)
+        self.prioritized = True
+
+    def set_beta(self, beta: float) -> None:
+        """Importance-weight exponent; a device scalar, so captured
+        launches see the annealing."""
+        self._beta_dev.fill_(float(beta))
+
+    def per_levels(self) -> t.List[torch.Tensor]:
+        """The L+1 unpadded levels of the sum tree, root first (views)."""
+        return [p[:n] for p, n in zip(self._per_pad, self._per_n)]
+
+    def _per_refresh(self, leaves: torch.Tensor) -> None:
+        """Recompute every ancestor of the given leaves from its children
+        (never by a delta: the tree is a function of its leaves)."""
+        nodes = leaves
+        for k in range(self._per_L - 1, -1, -1):
+            nodes = torch.unique(nodes // PER_FAN)
+            kids = self._per_pad[k + 1].view(-1, PER_FAN)[nodes]
+            self._per_pad[k][nodes] = per_node_sum(kids)
+
+    def _per_store(self, start: int, count: int) -> None:
+        """Give the ``count`` slots from ``start`` (mod max_size) the
+        current max priority — one launch on the GPU, no host read."""
+        ext = self._native_ext()
+        if ext is not None:
+            ext.per_set_range(self._per_tree, self.max_size, start, count,
+                              self._max_priority)
+            return
+        slots = (start + torch.arange(count, device=self.device)) \
+            % self.max_size
+        self._per_pad[self._per_L][slots] = self._max_priority
+        self._per_refresh(slots)
+
+    def draw(self, u: torch.Tensor) -> t.Tuple[torch.Tensor, torch.Tensor]:
+        """(slot, probability) for fp32 targets ``u`` in [0, root) — plain
+        torch, the definition the descent kernels are tested against.
+
+        From the root, at every level: load the 64 children c of the
+        node, form the inclusive prefix P by Hillis-Steele (the kernel's
+        ``__shfl_up`` order), pick the first lane with P > u and c > 0
+        (the scan is not monotone in floating point, so without the c > 0
+        guard a zero child could win); if u rounded past the end the last
+        lane with c > 0; lane 0 in an empty tree.  Then u = max(u -
+        (P[pick] - c[pick]), 0) and descend.  prob = leaf / root, or 1 for
+        an empty tree."""
+        u = torch.as_tensor(u, dtype=torch.float32,
+                            device=self.device).clone()
+        node = torch.zeros(u.shape, dtype=torch.long, device=self.device)
+        lanes = torch.arange(PER_FAN, device=self.device)
+        leaf = torch.zeros_like(u)
+        for k in range(1, self._per_L + 1):
+            c = self._per_pad[k].view(-1, PER_FAN)[node]
+            P = c.clone()
+            for off in (1, 2, 4, 8, 16, 32):
+                P = torch.cat([P[..., :off], P[..., off:] + P[..., :-off]],
+                              dim=-1)
+            pos = c > 0
+            hit = pos & (P > u[..., None])
+            first = torch.where(hit, lanes, PER_FAN).amin(-1)
+            last = torch.where(pos, lanes, -1).amax(-1)
+            pick = torch.where(first < PER_FAN, first, last.clamp(min=0))
+            Pp = P.gather(-1, pick[..., None])[..., 0]
+            cp = c.gather(-1, pick[..., None])[..., 0]
+            u = (u - (Pp - cp)).clamp(min=0)
+            node = node * PER_FAN + pick
+            leaf = cp
+        root = self._per_pad[0][0]
+        prob = torch.where(root == 0, torch.ones_like(leaf), leaf / root)
+        return node, prob
+
+    def _update_priorities_ref(self, idx: torch.Tensor,
+                               td: torch.Tensor) -> None:
+        """Plain-torch definition of ``update_priorities`` (and its CPU
+        path): p = (td + eps)^alpha in fp32; where a slot occurs more than
+        once the highest batch position wins; max_priority grows to the
+        largest p; all ancestors are recomputed."""
+        idx = torch.as_tensor(idx, dtype=torch.long,
+                              device=self.device).reshape(-1)
+        td = torch.as_tensor(td, dtype=torch.float32,
+                             device=self.device).reshape(-1)
+        p = (td + self.per_eps) ** self.per_alpha
+        uniq, inv = torch.unique(idx, return_inverse=True)
+        pos = torch.arange(idx.numel(), device=self.device)
+        win = torch.zeros_like(uniq).scatter_reduce(0, inv, pos, "amax")
+        self._per_pad[self._per_L][uniq] = p[win]
+        torch.maximum(self._max_priority, p.max().reshape(1),
+                      out=self._max_priority)
+        self._per_refresh(uniq)
+
+    def update_priorities(self, idx: torch.Tensor, td: torch.Tensor) -> None:
+        """New priorities ``(td + eps)^alpha`` for the slots ``idx`` from
+        their absolute TD errors ``td``; see ``_update_priorities_ref``."""
+        ext = self._native_ext()
+        if ext is None:
+            self._update_priorities_ref(idx, td)
+            return
+        idx = torch.as_tensor(idx, dtype=torch.long,
+                              device=self.device).reshape(-1).contiguous()
+        td = torch.as_tensor(td, dtype=torch.float32,
+                             device=self.device).reshape(-1).contiguous()
+        ext.per_update(self._per_tree, self.max_size, idx, td,
+                       self.per_alpha, self.per_eps, self._max_priority)
+
+    def is_weights(self, prob: torch.Tensor) -> torch.Tensor:
+        """Importance weights (size * prob)^-beta over their batch maximum
+        (plain torch, no host sync; the fused engine forms the same inside
+        its loss kernel)."""
+        w = (self._size_dev.to(torch.float32) * prob) ** (-self._beta_dev)
+        return w / w.max()
+
+    def _per_targets(self, batch_size: int) -> torch.Tensor:
+        """Stratified fp32 targets u_j = (j + u01_j) * (root / B) from the
+        host generator (CPU sampling; the kernels draw u01 from Philox)."""
+        u01 = torch.as_tensor(
+            self._rng.random(batch_size, dtype=np.float32),
+            device=self.device)
+        j = torch.arange(batch_size, dtype=torch.float32, device=self.device)
+        seg = self._per_pad[0][0] / torch.tensor(
+            float(batch_size), dtype=torch.float32, device=self.device)
+        return (j + u01) * seg
+
     # -- store ----------------------------------------------------------
 
     def _to_dev(self, x, shape) -> torch.Tensor:
@@ -121,6 +317,8 @@ class ReplayBuffer:
         self.done[i] = float(done)
         if self.episode_end is not None:
             self.episode_end[i] = float(done if end is None else end)
+        if self.prioritized:
+            self._per_store(i, 1)
         self.ptr = (self.ptr + 1) % self.max_size
         self.size = min(self.size + 1, self.max_size)
         self._size_dev.fill_(self.size)
@@ -154,6 +352,8 @@ class ReplayBuffer:
             dst[self.ptr:self.ptr + first].copy_(src[:first], non_blocking=True)
             if n > first:
                 dst[:n - first].copy_(src[first:], non_blocking=True)
+        if self.prioritized and n > 0:
+            self._per_store(self.ptr, n)
         self.ptr = (self.ptr + n) % self.max_size
         self.size = min(self.size + n_total, self.max_size)
         self._size_dev.fill_(self.size)
@@ -170,8 +370,27 @@ class ReplayBuffer:
             return require_extension()
         return None
 
+    def _per_args(self):
+        """Ring + tree arguments shared by the prioritized samplers; the
+        n-step fields are placeholders while n_step == 1."""
+        nstep = self.n_step > 1
+        return (self.state, self.actions, self.rewards, self.next_state,
+                self.done, self.episode_end if nstep else self.done,
+                self._size_dev, self._ptr_dev if nstep else self._size_dev,
+                self._per_tree, self._philox, self._philox_seed,
+                self.n_step, self.gamma)
+
     def sample(self, batch_size: int) -> Batch:
         ext = self._native_ext()
+        if self.prioritized and ext is not None:
+            s, a, r, ns, d, idx, prob = ext.replay_sample_p(
+                *self._per_args(), batch_size)
+            return Batch(s, a, r, ns, d, idx, self.is_weights(prob))
+        if self.prioritized:
+            idx, prob = self.draw(self._per_targets(batch_size))
+            b = self.sample_at(idx)
+            return Batch(b.states, b.actions, b.rewards, b.next_states,
+                         b.done, idx, self.is_weights(prob))
         if ext is not None and self.n_step > 1:
             s, a, r, ns, d = ext.replay_sample_n(
                 self.state, self.actions, self.rewards, self.next_state,
@@ -192,15 +411,40 @@ class ReplayBuffer:
     def make_static_batch(self, batch_size: int) -> Batch:
         """Preallocated batch tensors for hipGraph-captured sampling."""
         f32 = dict(dtype=torch.float32, device=self.device)
+        per = ()
+        if self.prioritized:
+            per = (torch.zeros(batch_size, dtype=torch.int64,
+                               device=self.device),
+                   torch.zeros(batch_size, **f32))
         return Batch(torch.zeros(batch_size, self.obs_dim, **f32),
                      torch.zeros(batch_size, self.act_dim, **f32),
                      torch.zeros(batch_size, **f32),
                      torch.zeros(batch_size, self.obs_dim, **f32),
-                     torch.zeros(batch_size, **f32))
+                     torch.zeros(batch_size, **f32), *per)
 
     def sample_into(self, out: Batch) -> None:
         """Graph-capturable sampling into preallocated batch tensors."""
         ext = self._native_ext()
+        if self.prioritized:
+            if out.indices is None or out.weights is None:
+                raise ValueError("prioritized sample_into needs a batch "
+                                 "from make_static_batch after "
+                                 "set_prioritized")
+            if ext is not None:
+                # probabilities land in out.weights, then become weights
+                ext.replay_sample_into_p(
+                    *self._per_args(), out.states, out.actions, out.rewards,
+                    out.next_states, out.done, out.indices, out.weights)
+                out.weights.copy_(self.is_weights(out.weights))
+                return
+            b = self.sample(out.states.shape[0])
+            for dst, src in zip(
+                    (out.states, out.actions, out.rewards, out.next_states,
+                     out.done, out.indices, out.weights),
+                    (b.states, b.actions, b.rewards, b.next_states, b.done,
+                     b.indices, b.weights)):
+                dst.copy_(src)
+            return
         if ext is not None and self.n_step > 1:
             ext.replay_sample_into_n(
                 self.state, self.actions, self.rewards, self.next_state,

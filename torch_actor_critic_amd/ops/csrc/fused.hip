@@ -1426,6 +1426,291 @@ void gather2n_kernel(const float* __restrict__ state,
 }
 
 // ---------------------------------------------------------------------------
+// Prioritized replay: fan-out-64 sum tree (buffer/replay.py::per_layout is
+// the layout, ::draw and ::_update_priorities_ref the executable definitions)
+// ---------------------------------------------------------------------------
+
+constexpr int PER_MAXL = 8;
+
+// Level k (0 = root, L = leaves) holds n[k] nodes at tree + off[k], padded
+// with zeros to a multiple of 64 so a wave always loads 64 in-bounds children.
+struct PerLay {
+  int L;
+  int64_t off[PER_MAXL];
+  int64_t n[PER_MAXL];
+};
+
+inline PerLay per_layout(int64_t cap, int64_t* total) {
+  PerLay lay;
+  int L = 1;
+  for (int64_t span = 64; span < cap; span *= 64) ++L;
+  TORCH_CHECK(cap >= 1 && L < PER_MAXL, "per: unsupported ring capacity");
+  lay.L = L;
+  lay.n[L] = cap;
+  for (int k = L - 1; k >= 0; --k) lay.n[k] = (lay.n[k + 1] + 63) / 64;
+  int64_t o = 0;
+  for (int k = 0; k <= L; ++k) {
+    lay.off[k] = o;
+    o += (lay.n[k] + 63) / 64 * 64;
+  }
+  for (int k = L + 1; k < PER_MAXL; ++k) lay.off[k] = lay.n[k] = 0;
+  *total = o;
+  return lay;
+}
+
+// Sum-tree descent for one target u — same code as
+// tac_kernels.hip::per_descend, duplicated to keep both translation units
+// self-contained.  Run by ONE full wave: per level, lane l loads child l of
+// the current node, a Hillis-Steele __shfl_up scan forms the inclusive
+// prefix P, and a ballot picks the first lane with P > u and c > 0 (the
+// scan is not monotone in floating point, so a zero child must not win);
+// if u rounded past the end, the last lane with c > 0; lane 0 in an empty
+// tree.  One dependent load per level.  All lanes return the same values.
+DEVINL int64_t per_descend_(const float* __restrict__ tree,
+                            const PerLay& lay, float u, float* prob) {
+  const int lane = threadIdx.x & 63;
+  int64_t node = 0;
+  float leaf = 0.f;
+  for (int k = 1; k <= lay.L; ++k) {
+    const float c = tree[lay.off[k] + node * 64 + lane];
+    float P = c;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const float t = __shfl_up(P, off);
+      if (lane >= off) P += t;
+    }
+    const bool pos = c > 0.f;
+    const unsigned long long hit = __ballot(pos && P > u);
+    const unsigned long long any = __ballot(pos);
+    const int pick = hit ? __ffsll((long long)hit) - 1
+                         : (any ? 63 - __clzll((long long)any) : 0);
+    const float Pp = __shfl(P, pick), cp = __shfl(c, pick);
+    u = fmaxf(u - (Pp - cp), 0.f);
+    node = node * 64 + pick;
+    leaf = cp;
+  }
+  const float root = tree[lay.off[0]];
+  *prob = root == 0.f ? 1.f : leaf / root;
+  return node;
+}
+
+// Stratified target of batch position j: u = (j + u01) * (root / B) with
+// u01 = (r.x >> 8) * 2^-24 from the Philox draw gather2 already makes.
+DEVINL float per_target_(const float* __restrict__ tree, const PerLay& lay,
+                         uint32_t rx, int j, int B) {
+#pragma clang fp contract(off)
+  const float u01 = (float)(rx >> 8) * 5.9604644775390625e-8f;
+  const float seg = tree[lay.off[0]] / (float)B;
+  return ((float)j + u01) * seg;
+}
+
+// gather2 drawing from the sum tree: same grid, output layout and Philox
+// keying as gather2_kernel.  Wave 0 descends and hands the slot to the
+// block through LDS; for n > 1 it then walks the n-step window from that
+// slot exactly as gather2n_kernel does.  Also writes the drawn slot, its
+// probability leaf / root and (tests only, when u_out is given) the target.
+__global__ __launch_bounds__(256)
+void gather2p_kernel(const float* __restrict__ state,
+                     const float* __restrict__ act,
+                     const float* __restrict__ rew,
+                     const float* __restrict__ nstate,
+                     const float* __restrict__ done,
+                     const float* __restrict__ ep_end,
+                     const int64_t* __restrict__ size_dev,
+                     const int64_t* __restrict__ ptr_dev,
+                     const float* __restrict__ tree, PerLay lay,
+                     const int64_t* __restrict__ ctr, int64_t ctr_add,
+                     uint64_t seed,
+                     float* __restrict__ xc,   // [2B, ldc]
+                     float* __restrict__ xc2,  // [B, ldc]
+                     float* __restrict__ orew, float* __restrict__ od,
+                     int64_t* __restrict__ idx_out,
+                     float* __restrict__ prob_out, float* __restrict__ u_out,
+                     int B, int obs_dim, int act_dim, int ldc,
+                     int64_t cap, int n, float gamma) {
+  __shared__ int64_t s_idx, s_last;
+  const int j = blockIdx.x;
+  if (threadIdx.x < 64) {
+    P4 r = philox_(seed, (uint64_t)(ctr[0] + ctr_add), (uint64_t)j);
+    const float u = per_target_(tree, lay, r.x, j, B);
+    float prob;
+    int64_t idx = per_descend_(tree, lay, u, &prob);
+    // a consistent tree never leads past the ring; keep the copies in
+    // bounds whatever the tree holds
+    idx = idx < cap ? idx : cap - 1;
+    int64_t last = idx;
+    float R, de;
+    if (n > 1) {
+      const int64_t size = size_dev[0];
+      const int64_t newest = size ? (ptr_dev[0] + cap - 1) % cap : 0;
+      last = nstep_walk_(rew, done, ep_end, idx, cap, newest, n, gamma, &R,
+                         &de);
+    } else {
+      R = rew[idx];
+      de = done[idx];
+    }
+    if (threadIdx.x == 0) {
+      s_idx = idx;
+      s_last = last;
+      orew[j] = R;
+      od[j] = de;
+      idx_out[j] = idx;
+      prob_out[j] = prob;
+      if (u_out) u_out[j] = u;
+    }
+  }
+  __syncthreads();
+  const int64_t idx = s_idx;
+  const float* srow = state + idx * obs_dim;
+  const float* nrow = nstate + s_last * obs_dim;
+  const float* arow = act + idx * act_dim;
+  for (int c = threadIdx.x; c < obs_dim; c += blockDim.x) {
+    float s = srow[c];
+    xc[(int64_t)j * ldc + c] = s;           // s -> XC rows :B
+    xc2[(int64_t)j * ldc + c] = s;          // s -> XC2
+    xc[(int64_t)(B + j) * ldc + c] = nrow[c];  // ns[last] -> XC rows B:
+  }
+  for (int c = threadIdx.x; c < act_dim; c += blockDim.x)
+    xc[(int64_t)j * ldc + obs_dim + c] = arow[c];  // a -> XC rows :B
+}
+
+constexpr int PER_THREADS = 1024;   // 16 waves: 16 nodes per load round trip
+
+// Recompute `count` nodes of level k from their children, one wave per
+// node: node_of(t) names the t-th node.  The sum is the fixed halving
+// order a __shfl_down reduction leaves in lane 0 (never a delta), so the
+// tree is a deterministic function of its leaves; naming a node twice
+// only stores the same value twice.  Two nodes per wave and round, so
+// their loads are in flight together.
+template <typename F>
+DEVINL void per_resum_(float* __restrict__ tree, const PerLay& lay, int k,
+                       int64_t count, F node_of) {
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const float* kids = tree + lay.off[k + 1];
+  float* out = tree + lay.off[k];
+  for (int64_t t0 = (int64_t)wave * 2; t0 < count; t0 += 2 * nw) {
+    const bool two = t0 + 1 < count;
+    const int64_t a = node_of(t0), b = two ? node_of(t0 + 1) : a;
+    float va = kids[a * 64 + lane], vb = kids[b * 64 + lane];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      va += __shfl_down(va, off);
+      vb += __shfl_down(vb, off);
+    }
+    if (lane == 0) {
+      out[a] = va;
+      if (two) out[b] = vb;
+    }
+  }
+}
+
+// update_priorities in one launch: p = (td + eps)^alpha into the leaves
+// (where a slot occurs more than once the highest batch position wins),
+// max_priority = max(max_priority, max p), then every ancestor level by
+// level.  Single block: all leaf writes must be complete before a parent
+// is summed and there is no grid-wide barrier.  Plain vector stores only.
+__global__ __launch_bounds__(PER_THREADS)
+void per_update_kernel(float* __restrict__ tree, PerLay lay,
+                       const int64_t* __restrict__ idx,
+                       const float* __restrict__ td, int B, float alpha,
+                       float eps, float* __restrict__ max_priority) {
+  __shared__ float red[PER_THREADS / 64];
+  // the first PER_THREADS slots, so the parent levels below need no second
+  // dependent load for them
+  __shared__ int64_t s_slot[PER_THREADS];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const int64_t cap = lay.n[lay.L];
+  float* leaves = tree + lay.off[lay.L];
+  // read up front so its latency hides under the leaf writes
+  float mp0 = 0.f;
+  if (threadIdx.x == 0) mp0 = max_priority[0];
+  float pmax = 0.f;
+  // Chunks of blockDim positions in ascending order.  Inside a wave a lane
+  // yields to any later lane with the same slot; the waves of a chunk that
+  // hold positions then store in wave order with a barrier in between, and
+  // the chunks follow each other, so the last store to a slot is its
+  // highest position's.
+  for (int j0 = 0; j0 < B; j0 += blockDim.x) {
+    const int j = j0 + threadIdx.x;
+    const bool live = j < B;
+    int64_t slot = live ? idx[j] : -1;
+    if (slot >= cap) slot = -1;      // never write outside the ring
+    if (j0 == 0) s_slot[threadIdx.x] = slot;
+    float p = 0.f;
+    bool win = slot >= 0;
+    if (j0 + wave * 64 < B) {        // wave-uniform: the wave has positions
+      if (live) {
+        p = powf(td[j] + eps, alpha);
+        pmax = fmaxf(pmax, p);
+      }
+      for (int m = 1; m < 64; ++m) {
+        const int64_t other = __shfl(slot, m);
+        if (m > lane && other == slot) win = false;
+      }
+    }
+    const int left = B - j0;
+    const int busy = left >= (int)blockDim.x ? nw : (left + 63) >> 6;
+    for (int w = 0; w < busy; ++w) {
+      if (w == wave && win) leaves[slot] = p;
+      __syncthreads();
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1)
+    pmax = fmaxf(pmax, __shfl_down(pmax, off));
+  if (lane == 0) red[wave] = pmax;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float m = mp0;
+    for (int w = 0; w < nw; ++w) m = fmaxf(m, red[w]);
+    max_priority[0] = m;
+  }
+  for (int k = lay.L - 1; k >= 0; --k) {
+    const int shift = 6 * (lay.L - k);
+    if (lay.n[k] <= B) {
+      // a small level: every node, no index reads
+      per_resum_(tree, lay, k, lay.n[k], [](int64_t t) { return t; });
+    } else {
+      per_resum_(tree, lay, k, B, [&](int64_t t) {
+        const int64_t s = t < PER_THREADS ? s_slot[t] : idx[t];
+        return (s >= 0 && s < cap ? s : 0) >> shift;
+      });
+    }
+    __syncthreads();
+  }
+}
+
+// store / store_batch: the `count` slots from `start` (mod cap) get the
+// device scalar max_priority — no host read — and their ancestors are
+// recomputed.  A wrapping range is two runs of nodes on every level.
+__global__ __launch_bounds__(PER_THREADS)
+void per_set_range_kernel(float* __restrict__ tree, PerLay lay,
+                          int64_t start, int64_t count,
+                          const float* __restrict__ max_priority) {
+  const int64_t cap = lay.n[lay.L];
+  float* leaves = tree + lay.off[lay.L];
+  const float p = max_priority[0];
+  const int64_t first = count < cap - start ? count : cap - start;
+  for (int64_t i = threadIdx.x; i < count; i += blockDim.x)
+    leaves[i < first ? start + i : i - first] = p;
+  __syncthreads();
+  // inclusive leaf runs [a0, b0] and, when the range wraps, [0, b1]
+  const int64_t a0 = start, b0 = start + first - 1, b1 = count - first - 1;
+  for (int k = lay.L - 1; k >= 0; --k) {
+    const int shift = 6 * (lay.L - k);
+    const int64_t lo = a0 >> shift;
+    const int64_t len0 = (b0 >> shift) - lo + 1;
+    const int64_t len1 = b1 >= 0 ? (b1 >> shift) + 1 : 0;
+    per_resum_(tree, lay, k, len0 + len1, [&](int64_t t) {
+      return t < len0 ? lo + t : t - len0;
+    });
+    __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Fused tanh-Gaussian head, stacked rows with split outputs + internal
 // Philox noise (row < B0 -> out0 slice; else out1 slice)
 // ---------------------------------------------------------------------------
@@ -1534,6 +1819,11 @@ void tg_bwd2_kernel(const float* __restrict__ dxc, int ld_dxc, int col0,
 // (outer product; dq staged in LDS so no extra launch is needed).
 constexpr int LOSS_MAXB = 1024;
 
+// WEIGHTED (prioritized replay): importance weights w_j = (size * prob_j)^
+// -beta over their batch maximum scale each row's squared errors and its
+// gradient seeds, and td_j = (|e1| + |e2|) / 2 is exported for the priority
+// update.  The default instantiation compiles to the unweighted kernel.
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256)
 void qloss2_kernel(const float* __restrict__ q1, const float* __restrict__ q2,
                    const float* __restrict__ q1t, const float* __restrict__ q2t,
@@ -1548,7 +1838,11 @@ void qloss2_kernel(const float* __restrict__ q1, const float* __restrict__ q2,
                    float* __restrict__ dy2_0, float* __restrict__ dy2_1,
                    int h2,
                    int64_t* __restrict__ bump0, int64_t* __restrict__ bump1,
-                   int64_t* __restrict__ bump2) {
+                   int64_t* __restrict__ bump2,
+                   const float* __restrict__ prob,
+                   const int64_t* __restrict__ size_dev,
+                   const float* __restrict__ beta_dev,
+                   float* __restrict__ td) {
   __shared__ float red[4];
   __shared__ float dqs[2][LOSS_MAXB];
   const float alpha = alpha_dev ? alpha_dev[0] : alpha_host;
@@ -1560,13 +1854,38 @@ void qloss2_kernel(const float* __restrict__ q1, const float* __restrict__ q2,
     if (bump1) c1 = bump1[0];
     if (bump2) c2 = bump2[0];
   }
+  float wsize = 0.f, nbeta = 0.f, wmax = 1.f;
+  if constexpr (WEIGHTED) {
+    // batch maximum of the raw weights first (max is order-independent)
+    __shared__ float redw[4];
+    wsize = (float)size_dev[0];
+    nbeta = -beta_dev[0];
+    float m = 0.f;
+    for (int i = threadIdx.x; i < B; i += blockDim.x)
+      m = fmaxf(m, powf(wsize * prob[i], nbeta));
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_down(m, off));
+    if ((threadIdx.x & 63) == 0) redw[threadIdx.x >> 6] = m;
+    __syncthreads();
+    wmax = fmaxf(fmaxf(redw[0], redw[1]), fmaxf(redw[2], redw[3]));
+  }
   float acc = 0.f;
   for (int i = threadIdx.x; i < B; i += blockDim.x) {
     float backup = scale * rew[i] + gamma * (1.f - done[i]) *
                        (fminf(q1t[i], q2t[i]) - alpha * logp_next[i]);
     float e1 = q1[i] - backup, e2 = q2[i] - backup;
-    acc += e1 * e1 + e2 * e2;
-    float g1 = 2.f * e1 / B, g2 = 2.f * e2 / B;
+    float g1, g2;
+    if constexpr (WEIGHTED) {
+      const float w = powf(wsize * prob[i], nbeta) / wmax;
+      acc += w * (e1 * e1 + e2 * e2);
+      g1 = 2.f * (w * e1) / B;
+      g2 = 2.f * (w * e2) / B;
+      td[i] = 0.5f * (fabsf(e1) + fabsf(e2));
+    } else {
+      acc += e1 * e1 + e2 * e2;
+      g1 = 2.f * e1 / B;
+      g2 = 2.f * e2 / B;
+    }
     dq1[i] = g1;
     dq2[i] = g2;
     if (fuse) { dqs[0][i] = g1; dqs[1][i] = g2; }
@@ -2487,6 +2806,107 @@ void gather2n(torch::Tensor state, torch::Tensor act, torch::Tensor rew,
                      (float)gamma);
 }
 
+// The sum tree of a ring with `cap` slots; checks the flat tensor against
+// the layout every per_* launch indexes it with.
+PerLay per_tree_layout(const torch::Tensor& tree, int64_t cap,
+                       const char* who) {
+  int64_t total = 0;
+  PerLay lay = per_layout(cap, &total);
+  TORCH_CHECK(tree.is_cuda() && tree.is_contiguous() &&
+              tree.dtype() == torch::kFloat32 && tree.numel() == total,
+              who, ": tree must be a contiguous fp32 device tensor of ",
+              total, " elements for a ring of ", cap);
+  return lay;
+}
+
+void gather2p(torch::Tensor state, torch::Tensor act, torch::Tensor rew,
+              torch::Tensor nstate, torch::Tensor done, torch::Tensor ep_end,
+              torch::Tensor size_dev, torch::Tensor ptr_dev,
+              torch::Tensor tree, torch::Tensor ctr, int64_t seed, int64_t n,
+              double gamma, torch::Tensor xc, torch::Tensor xc2,
+              torch::Tensor orew, torch::Tensor od, torch::Tensor idx_out,
+              torch::Tensor prob_out, c10::optional<torch::Tensor> u_out,
+              int64_t B, int64_t ctr_add) {
+  const int obs_dim = (int)state.size(1);
+  const int act_dim = (int)act.size(1);
+  const int64_t cap = state.size(0);
+  TORCH_CHECK(n >= 1 && n <= 64, "n_step must be in 1..64");
+  for (const torch::Tensor& t : {state, act, rew, nstate, done, ep_end, xc,
+                                 xc2, orew, od, prob_out})
+    TORCH_CHECK(t.is_cuda() && t.is_contiguous() &&
+                t.dtype() == torch::kFloat32,
+                "gather2p: tensors must be contiguous fp32 device tensors");
+  TORCH_CHECK(cap >= 1 && rew.numel() == cap && done.numel() == cap &&
+              ep_end.numel() == cap && nstate.size(0) == cap &&
+              nstate.size(1) == obs_dim && act.size(0) == cap,
+              "gather2p: ring fields must share one capacity");
+  TORCH_CHECK(ptr_dev.is_cuda() && ptr_dev.dtype() == torch::kInt64 &&
+              ptr_dev.numel() == 1 && size_dev.is_cuda() &&
+              size_dev.dtype() == torch::kInt64 && size_dev.numel() == 1,
+              "gather2p: size_dev / ptr_dev must be int64 [1] device tensors");
+  TORCH_CHECK(B >= 1 && xc.size(0) >= 2 * B && xc2.size(0) >= B &&
+              xc.size(1) >= obs_dim + act_dim && xc2.size(1) == xc.size(1) &&
+              orew.numel() >= B && od.numel() >= B && prob_out.numel() >= B &&
+              idx_out.is_cuda() && idx_out.is_contiguous() &&
+              idx_out.dtype() == torch::kInt64 && idx_out.numel() >= B,
+              "gather2p: batch buffers too small");
+  TORCH_CHECK(!u_out.has_value() ||
+              (u_out->is_cuda() && u_out->is_contiguous() &&
+               u_out->dtype() == torch::kFloat32 && u_out->numel() >= B),
+              "gather2p: bad u_out");
+  PerLay lay = per_tree_layout(tree, cap, "gather2p");
+  int threads = std::min<int>(256, std::max(64, ((obs_dim + 63) / 64) * 64));
+  hipLaunchKernelGGL(gather2p_kernel, dim3((int)B), dim3(threads), 0,
+                     stream(),
+                     state.data_ptr<float>(), act.data_ptr<float>(),
+                     rew.data_ptr<float>(), nstate.data_ptr<float>(),
+                     done.data_ptr<float>(), ep_end.data_ptr<float>(),
+                     size_dev.data_ptr<int64_t>(),
+                     ptr_dev.data_ptr<int64_t>(), tree.data_ptr<float>(),
+                     lay, ctr.data_ptr<int64_t>(), ctr_add, (uint64_t)seed,
+                     xc.data_ptr<float>(), xc2.data_ptr<float>(),
+                     orew.data_ptr<float>(), od.data_ptr<float>(),
+                     idx_out.data_ptr<int64_t>(), prob_out.data_ptr<float>(),
+                     u_out.has_value() ? u_out->data_ptr<float>() : nullptr,
+                     (int)B, obs_dim, act_dim, (int)xc.size(1), cap, (int)n,
+                     (float)gamma);
+}
+
+void per_update(torch::Tensor tree, int64_t cap, torch::Tensor idx,
+                torch::Tensor td, double alpha, double eps,
+                torch::Tensor max_priority) {
+  PerLay lay = per_tree_layout(tree, cap, "per_update");
+  const int64_t B = idx.numel();
+  TORCH_CHECK(B >= 1 && B < (int64_t(1) << 31) && idx.is_cuda() &&
+              idx.is_contiguous() && idx.dtype() == torch::kInt64 &&
+              td.is_cuda() && td.is_contiguous() &&
+              td.dtype() == torch::kFloat32 && td.numel() >= B,
+              "per_update: idx must be int64 [B], td fp32 [B], on the device");
+  TORCH_CHECK(max_priority.is_cuda() &&
+              max_priority.dtype() == torch::kFloat32 &&
+              max_priority.numel() == 1,
+              "per_update: max_priority must be an fp32 [1] device tensor");
+  hipLaunchKernelGGL(per_update_kernel, dim3(1), dim3(PER_THREADS), 0,
+                     stream(), tree.data_ptr<float>(), lay,
+                     idx.data_ptr<int64_t>(), td.data_ptr<float>(), (int)B,
+                     (float)alpha, (float)eps,
+                     max_priority.data_ptr<float>());
+}
+
+void per_set_range(torch::Tensor tree, int64_t cap, int64_t start,
+                   int64_t count, torch::Tensor max_priority) {
+  PerLay lay = per_tree_layout(tree, cap, "per_set_range");
+  TORCH_CHECK(start >= 0 && start < cap && count >= 1 && count <= cap,
+              "per_set_range: range outside the ring");
+  TORCH_CHECK(max_priority.is_cuda() &&
+              max_priority.dtype() == torch::kFloat32 &&
+              max_priority.numel() == 1,
+              "per_set_range: max_priority must be an fp32 [1] device tensor");
+  hipLaunchKernelGGL(per_set_range_kernel, dim3(1), dim3(PER_THREADS), 0,
+                     stream(), tree.data_ptr<float>(), lay, start, count,
+                     max_priority.data_ptr<float>());
+}
+
 void tg_fwd2(torch::Tensor hl, torch::Tensor out0,
              int64_t col0, torch::Tensor out1, int64_t col1, int64_t B0,
              torch::Tensor logp, torch::Tensor prob, torch::Tensor ctr,
@@ -2531,13 +2951,32 @@ void qloss2(torch::Tensor q1, torch::Tensor q2, torch::Tensor q1t,
             c10::optional<torch::Tensor> dy2_1, int64_t h2,
             c10::optional<torch::Tensor> bump0,
             c10::optional<torch::Tensor> bump1,
-            c10::optional<torch::Tensor> bump2) {
+            c10::optional<torch::Tensor> bump2,
+            c10::optional<torch::Tensor> prob,
+            c10::optional<torch::Tensor> size_dev,
+            c10::optional<torch::Tensor> beta_dev,
+            c10::optional<torch::Tensor> td) {
   const bool fuse = dy2_0.has_value();
   TORCH_CHECK(!fuse || B <= LOSS_MAXB);
   auto iptr = [](const c10::optional<torch::Tensor>& t) -> int64_t* {
     return t.has_value() ? t->data_ptr<int64_t>() : nullptr;
   };
-  hipLaunchKernelGGL(qloss2_kernel, dim3(1), dim3(256), 0, stream(),
+  const bool weighted = prob.has_value();
+  if (weighted) {
+    TORCH_CHECK(size_dev.has_value() && beta_dev.has_value() &&
+                td.has_value(),
+                "qloss2: prob needs size_dev, beta_dev and td");
+    TORCH_CHECK(prob->is_cuda() && prob->is_contiguous() &&
+                prob->dtype() == torch::kFloat32 && prob->numel() >= B &&
+                td->is_cuda() && td->is_contiguous() &&
+                td->dtype() == torch::kFloat32 && td->numel() >= B &&
+                beta_dev->is_cuda() && beta_dev->dtype() == torch::kFloat32 &&
+                beta_dev->numel() == 1 && size_dev->is_cuda() &&
+                size_dev->dtype() == torch::kInt64 && size_dev->numel() == 1,
+                "qloss2: bad prioritized-replay arguments");
+  }
+  auto kernel = weighted ? qloss2_kernel<true> : qloss2_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(1), dim3(256), 0, stream(),
                      q1.data_ptr<float>(), q2.data_ptr<float>(),
                      q1t.data_ptr<float>(), q2t.data_ptr<float>(),
                      logp_next.data_ptr<float>(), rew.data_ptr<float>(),
@@ -2548,7 +2987,10 @@ void qloss2(torch::Tensor q1, torch::Tensor q2, torch::Tensor q1t,
                      fptr(wt3_0), fptr(wt3_1),
                      fuse ? dy2_0->data_ptr<float>() : nullptr,
                      fuse ? dy2_1->data_ptr<float>() : nullptr, (int)h2,
-                     iptr(bump0), iptr(bump1), iptr(bump2));
+                     iptr(bump0), iptr(bump1), iptr(bump2), fptr(prob),
+                     weighted ? size_dev->data_ptr<int64_t>() : nullptr,
+                     fptr(beta_dev),
+                     weighted ? td->data_ptr<float>() : nullptr);
 }
 
 void piloss2(torch::Tensor q1, torch::Tensor q2, torch::Tensor logp,
@@ -2855,6 +3297,17 @@ void register_fused(pybind11::module_& m) {
         py::arg("ctr"), py::arg("seed"), py::arg("n"), py::arg("gamma"),
         py::arg("xc"), py::arg("xc2"), py::arg("orew"), py::arg("od"),
         py::arg("B"), py::arg("ctr_add") = 0);
+  m.def("gather2p", &fused::gather2p, py::arg("state"), py::arg("act"),
+        py::arg("rew"), py::arg("nstate"), py::arg("done"),
+        py::arg("ep_end"), py::arg("size_dev"), py::arg("ptr_dev"),
+        py::arg("tree"), py::arg("ctr"), py::arg("seed"), py::arg("n"),
+        py::arg("gamma"), py::arg("xc"), py::arg("xc2"), py::arg("orew"),
+        py::arg("od"), py::arg("idx_out"), py::arg("prob_out"),
+        py::arg("u_out"), py::arg("B"), py::arg("ctr_add") = 0);
+  m.def("per_update", &fused::per_update,
+        "sum tree: leaves[idx] = (td + eps)^alpha, ancestors recomputed");
+  m.def("per_set_range", &fused::per_set_range,
+        "sum tree: a ring range gets max_priority, ancestors recomputed");
   m.def("tg_fwd2", &fused::tg_fwd2, py::arg("hl"), py::arg("out0"),
         py::arg("col0"), py::arg("out1"), py::arg("col1"), py::arg("B0"),
         py::arg("logp"), py::arg("prob"), py::arg("ctr"), py::arg("seed"),
@@ -2868,7 +3321,9 @@ void register_fused(pybind11::module_& m) {
         py::arg("dq2"), py::arg("B"), py::arg("gamma"), py::arg("scale"),
         py::arg("wt3_0"), py::arg("wt3_1"), py::arg("dy2_0"),
         py::arg("dy2_1"), py::arg("h2"), py::arg("bump0") = py::none(),
-        py::arg("bump1") = py::none(), py::arg("bump2") = py::none());
+        py::arg("bump1") = py::none(), py::arg("bump2") = py::none(),
+        py::arg("prob") = py::none(), py::arg("size_dev") = py::none(),
+        py::arg("beta_dev") = py::none(), py::arg("td") = py::none());
   m.def("piloss2", &fused::piloss2);
   m.def("alpha_update", &fused::alpha_update);
   m.def("tg_eps", &fused::tg_eps);

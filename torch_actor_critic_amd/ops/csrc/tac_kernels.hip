@@ -817,6 +817,144 @@ void replay_gather_n_kernel(const float* __restrict__ state,
 }
 
 // ---------------------------------------------------------------------------
+// Prioritized replay sample + gather from the fan-out-64 sum tree
+// (buffer/replay.py::per_layout is the layout, ::draw the definition)
+// ---------------------------------------------------------------------------
+
+constexpr int PER_MAXL = 8;
+
+// Level k (0 = root, L = leaves) holds n[k] nodes at tree + off[k], padded
+// with zeros to a multiple of 64 so a wave always loads 64 in-bounds children.
+struct PerLay {
+  int L;
+  int64_t off[PER_MAXL];
+  int64_t n[PER_MAXL];
+};
+
+// Sum-tree descent for one target u, run by ONE full wave.  Per level,
+// lane l loads child l of the current node (one coalesced 256-byte load —
+// the fan-out is the wave width), a Hillis-Steele __shfl_up scan forms the
+// inclusive prefix P and a ballot picks the first lane with P > u and
+// c > 0.  The c > 0 guard is required: the scan is not monotone in
+// floating point, so without it a zero child could win.  If u rounded past
+// the end the last lane with c > 0 is taken, lane 0 in an empty tree.  The
+// remainder u - (P[pick] - c[pick]), clamped at 0, goes down one level:
+// L dependent loads per sample.  prob = leaf / root (1 for an empty tree).
+// All lanes return the same values.
+DEVINL int64_t per_descend(const float* __restrict__ tree, const PerLay& lay,
+                           float u, float* prob) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  int64_t node = 0;
+  float leaf = 0.f;
+  for (int k = 1; k <= lay.L; ++k) {
+    const float c = tree[lay.off[k] + node * 64 + lane];
+    float P = c;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const float t = __shfl_up(P, off);
+      if (lane >= off) P += t;
+    }
+    const bool pos = c > 0.f;
+    const unsigned long long hit = __ballot(pos && P > u);
+    const unsigned long long any = __ballot(pos);
+    const int pick = hit ? __ffsll((long long)hit) - 1
+                         : (any ? 63 - __clzll((long long)any) : 0);
+    const float Pp = __shfl(P, pick), cp = __shfl(c, pick);
+    u = fmaxf(u - (Pp - cp), 0.f);
+    node = node * 64 + pick;
+    leaf = cp;
+  }
+  const float root = tree[lay.off[0]];
+  *prob = root == 0.f ? 1.f : leaf / root;
+  return node;
+}
+
+// Stratified target of batch position j: u = (j + u01) * (root / B) with
+// u01 = (r.x >> 8) * 2^-24 from the Philox draw replay_gather_kernel makes.
+DEVINL float per_target(const float* __restrict__ tree, const PerLay& lay,
+                        uint32_t rx, int j, int B) {
+#pragma clang fp contract(off)
+  const float u01 = (float)(rx >> 8) * 5.9604644775390625e-8f;
+  const float seg = tree[lay.off[0]] / (float)B;
+  return ((float)j + u01) * seg;
+}
+
+// Same grid and Philox keying as replay_gather_kernel.  Wave 0 descends the
+// tree and hands the slot to the block through LDS; for n > 1 it then walks
+// the n-step window from that slot as replay_gather_n_kernel does.  Writes
+// the drawn slot, its probability and (when given) the target u.  With
+// os == nullptr nothing is gathered (the standalone per_sample binding).
+__global__ __launch_bounds__(256)
+void replay_gather_p_kernel(const float* __restrict__ state,
+                            const float* __restrict__ act,
+                            const float* __restrict__ rew,
+                            const float* __restrict__ nstate,
+                            const float* __restrict__ done,
+                            const float* __restrict__ ep_end,
+                            const int64_t* __restrict__ size_dev,
+                            const int64_t* __restrict__ ptr_dev,
+                            const float* __restrict__ tree, PerLay lay,
+                            const int64_t* __restrict__ ctr, uint64_t seed,
+                            float* __restrict__ os, float* __restrict__ oa,
+                            float* __restrict__ orew, float* __restrict__ ons,
+                            float* __restrict__ od,
+                            int64_t* __restrict__ idx_out,
+                            float* __restrict__ prob_out,
+                            float* __restrict__ u_out,
+                            int B, int obs_dim, int act_dim, int64_t cap,
+                            int n, float gamma) {
+  __shared__ int64_t s_idx, s_last;
+  const int j = blockIdx.x;
+  const bool gather = os != nullptr;
+  if (threadIdx.x < WAVE) {
+    Philox4 r = philox4(seed, (uint64_t)ctr[0], (uint64_t)j);
+    const float u = per_target(tree, lay, r.x, j, B);
+    float prob;
+    int64_t idx = per_descend(tree, lay, u, &prob);
+    // a consistent tree never leads past the ring; keep the copies in
+    // bounds whatever the tree holds
+    idx = idx < cap ? idx : cap - 1;
+    int64_t last = idx;
+    if (gather) {
+      float R, de;
+      if (n > 1) {
+        const int64_t size = size_dev[0];
+        const int64_t newest = size ? (ptr_dev[0] + cap - 1) % cap : 0;
+        last = nstep_walk(rew, done, ep_end, idx, cap, newest, n, gamma, &R,
+                          &de);
+      } else {
+        R = rew[idx];
+        de = done[idx];
+      }
+      if (threadIdx.x == 0) {
+        orew[j] = R;
+        od[j] = de;
+      }
+    }
+    if (threadIdx.x == 0) {
+      s_idx = idx;
+      s_last = last;
+      idx_out[j] = idx;
+      prob_out[j] = prob;
+      if (u_out) u_out[j] = u;
+    }
+  }
+  if (!gather) return;
+  __syncthreads();
+  const float* srow = state + s_idx * obs_dim;
+  const float* nrow = nstate + s_last * obs_dim;
+  float* osr = os + (int64_t)j * obs_dim;
+  float* onr = ons + (int64_t)j * obs_dim;
+  for (int c = threadIdx.x; c < obs_dim; c += blockDim.x) {
+    osr[c] = srow[c];
+    onr[c] = nrow[c];
+  }
+  const float* arow = act + s_idx * act_dim;
+  float* oar = oa + (int64_t)j * act_dim;
+  for (int c = threadIdx.x; c < act_dim; c += blockDim.x) oar[c] = arow[c];
+}
+
+// ---------------------------------------------------------------------------
 // Visual replay gather: ONE kernel draws the Philox index and copies
 // features / frames (with u8 -> f32 dequantization) / actions / rewards
 // / done into the static batch — replaces ~18 aten index/copy/decode
@@ -1201,6 +1339,110 @@ void replay_sample_into_n(torch::Tensor state, torch::Tensor act,
                      (float)gamma);
 }
 
+// Layout of the sum tree over `cap` leaves, checked against the flat tensor.
+PerLay per_tree_layout(const torch::Tensor& tree, int64_t cap) {
+  PerLay lay;
+  int L = 1;
+  for (int64_t span = 64; span < cap; span *= 64) ++L;
+  TORCH_CHECK(cap >= 1 && L < PER_MAXL, "per: unsupported ring capacity");
+  lay.L = L;
+  lay.n[L] = cap;
+  for (int k = L - 1; k >= 0; --k) lay.n[k] = (lay.n[k + 1] + 63) / 64;
+  int64_t total = 0;
+  for (int k = 0; k <= L; ++k) {
+    lay.off[k] = total;
+    total += (lay.n[k] + 63) / 64 * 64;
+  }
+  for (int k = L + 1; k < PER_MAXL; ++k) lay.off[k] = lay.n[k] = 0;
+  TORCH_CHECK(tree.is_cuda() && tree.is_contiguous() &&
+              tree.dtype() == torch::kFloat32 && tree.numel() == total,
+              "per: tree must be a contiguous fp32 device tensor of ", total,
+              " elements for a ring of ", cap);
+  return lay;
+}
+
+// Prioritized variant: slots come from the sum tree `tree` of the ring
+// (stratified, one Philox draw per batch row) instead of a uniform draw.
+// n == 1 ignores ep_end / ptr_dev.  Also writes the drawn slots and their
+// probabilities.
+void replay_sample_into_p(torch::Tensor state, torch::Tensor act,
+                          torch::Tensor rew, torch::Tensor nstate,
+                          torch::Tensor done, torch::Tensor ep_end,
+                          torch::Tensor size_dev, torch::Tensor ptr_dev,
+                          torch::Tensor tree, torch::Tensor ctr,
+                          int64_t seed, int64_t n, double gamma,
+                          torch::Tensor os, torch::Tensor oa,
+                          torch::Tensor orew, torch::Tensor ons,
+                          torch::Tensor od, torch::Tensor oidx,
+                          torch::Tensor oprob) {
+  CHECK_IN(state); CHECK_IN(act); CHECK_IN(rew); CHECK_IN(nstate);
+  CHECK_IN(done); CHECK_IN(ep_end);
+  CHECK_IN(os); CHECK_IN(oa); CHECK_IN(orew); CHECK_IN(ons); CHECK_IN(od);
+  CHECK_IN(oprob);
+  TORCH_CHECK(n >= 1 && n <= 64, "n_step must be in 1..64");
+  const int64_t cap = state.size(0);
+  TORCH_CHECK(cap >= 1 && rew.numel() == cap && done.numel() == cap &&
+              ep_end.numel() == cap && nstate.size(0) == cap &&
+              act.size(0) == cap, "ring fields must share one capacity");
+  TORCH_CHECK(ptr_dev.is_cuda() && ptr_dev.dtype() == torch::kInt64 &&
+              ptr_dev.numel() == 1 && size_dev.is_cuda() &&
+              size_dev.dtype() == torch::kInt64 && size_dev.numel() == 1,
+              "size_dev / ptr_dev must be int64 [1] device tensors");
+  const int B = os.size(0);
+  const int obs_dim = state.size(1);
+  const int act_dim = act.size(1);
+  TORCH_CHECK(B >= 1 && os.size(1) == obs_dim && ons.size(1) == obs_dim &&
+              ons.size(0) == B && oa.size(0) == B && oa.size(1) == act_dim &&
+              orew.numel() == B && od.numel() == B && oprob.numel() == B &&
+              oidx.is_cuda() && oidx.is_contiguous() &&
+              oidx.dtype() == torch::kInt64 && oidx.numel() == B,
+              "batch shape mismatch");
+  PerLay lay = per_tree_layout(tree, cap);
+  auto s = cur_stream();
+  hipLaunchKernelGGL(bump_counter_kernel, dim3(1), dim3(1), 0, s,
+                     ctr.data_ptr<int64_t>());
+  int threads = std::min(256, std::max(64, ((obs_dim + 63) / 64) * 64));
+  hipLaunchKernelGGL(replay_gather_p_kernel, dim3(B), dim3(threads), 0, s,
+                     state.data_ptr<float>(), act.data_ptr<float>(),
+                     rew.data_ptr<float>(), nstate.data_ptr<float>(),
+                     done.data_ptr<float>(), ep_end.data_ptr<float>(),
+                     size_dev.data_ptr<int64_t>(),
+                     ptr_dev.data_ptr<int64_t>(), tree.data_ptr<float>(),
+                     lay, ctr.data_ptr<int64_t>(), (uint64_t)seed,
+                     os.data_ptr<float>(), oa.data_ptr<float>(),
+                     orew.data_ptr<float>(), ons.data_ptr<float>(),
+                     od.data_ptr<float>(), oidx.data_ptr<int64_t>(),
+                     oprob.data_ptr<float>(), (float*)nullptr, B, obs_dim,
+                     act_dim, cap, (int)n, (float)gamma);
+}
+
+// The draw alone: (slot, probability, target u) for `batch` stratified
+// targets, no gather.  Bumps the counter like the samplers.
+std::vector<torch::Tensor> per_sample(torch::Tensor tree, int64_t cap,
+                                      torch::Tensor ctr, int64_t seed,
+                                      int64_t batch) {
+  PerLay lay = per_tree_layout(tree, cap);
+  TORCH_CHECK(batch >= 1 && batch < (int64_t(1) << 31), "bad batch size");
+  TORCH_CHECK(ctr.is_cuda() && ctr.dtype() == torch::kInt64 &&
+              ctr.numel() == 1, "ctr must be an int64 [1] device tensor");
+  auto oidx = torch::empty({batch}, tree.options().dtype(torch::kInt64));
+  auto oprob = torch::empty({batch}, tree.options());
+  auto ou = torch::empty({batch}, tree.options());
+  auto s = cur_stream();
+  hipLaunchKernelGGL(bump_counter_kernel, dim3(1), dim3(1), 0, s,
+                     ctr.data_ptr<int64_t>());
+  const float* nf = nullptr;
+  const int64_t* ni = nullptr;
+  float* nout = nullptr;
+  hipLaunchKernelGGL(replay_gather_p_kernel, dim3((int)batch), dim3(64), 0, s,
+                     nf, nf, nf, nf, nf, nf, ni, ni, tree.data_ptr<float>(),
+                     lay, ctr.data_ptr<int64_t>(), (uint64_t)seed, nout, nout,
+                     nout, nout, nout, oidx.data_ptr<int64_t>(),
+                     oprob.data_ptr<float>(), ou.data_ptr<float>(),
+                     (int)batch, 0, 0, cap, 1, 1.0f);
+  return {oidx, oprob, ou};
+}
+
 // One-kernel visual ring store: quantize both fp32 frames to u8 and
 // write every field of the transition at ring slot `idx` — replaces the
 // CPU-side encode chain + ~10 aten copies per env step.
@@ -1384,6 +1626,25 @@ std::vector<torch::Tensor> replay_sample_n(
   return {os, oa, orew, ons, od};
 }
 
+std::vector<torch::Tensor> replay_sample_p(
+    torch::Tensor state, torch::Tensor act, torch::Tensor rew,
+    torch::Tensor nstate, torch::Tensor done, torch::Tensor ep_end,
+    torch::Tensor size_dev, torch::Tensor ptr_dev, torch::Tensor tree,
+    torch::Tensor ctr, int64_t seed, int64_t n, double gamma,
+    int64_t batch) {
+  auto os = torch::empty({batch, state.size(1)}, state.options());
+  auto oa = torch::empty({batch, act.size(1)}, state.options());
+  auto orew = torch::empty({batch}, state.options());
+  auto ons = torch::empty({batch, state.size(1)}, state.options());
+  auto od = torch::empty({batch}, state.options());
+  auto oidx = torch::empty({batch}, state.options().dtype(torch::kInt64));
+  auto oprob = torch::empty({batch}, state.options());
+  replay_sample_into_p(state, act, rew, nstate, done, ep_end, size_dev,
+                       ptr_dev, tree, ctr, seed, n, gamma, os, oa, orew, ons,
+                       od, oidx, oprob);
+  return {os, oa, orew, ons, od, oidx, oprob};
+}
+
 }  // namespace
 
 // shared compute-mode flag for the fused-engine / conv TUs
@@ -1416,6 +1677,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("replay_sample_into", &replay_sample_into);
   m.def("replay_sample_n", &replay_sample_n);
   m.def("replay_sample_into_n", &replay_sample_into_n);
+  m.def("replay_sample_p", &replay_sample_p);
+  m.def("replay_sample_into_p", &replay_sample_into_p);
+  m.def("per_sample", &per_sample,
+        "sum-tree draw only: (slot, probability, target u)");
   m.def("visual_sample_into", &visual_sample_into);
   m.def("visual_store_into", &visual_store_into);
   m.def("philox_randn_", &philox_randn_);

@@ -679,9 +679,17 @@ class _NativeQLoss(torch.autograd.Function):
 
 
 def sac_q_loss(q1, q2, q1t, q2t, logp_next, rewards, done, alpha, gamma,
-               reward_scale):
+               reward_scale, weights=None):
     """Twin-Q Bellman MSE: loss = mse(q1, backup) + mse(q2, backup) with
-    backup = scale*r + gamma*(1-d)*(min(q1t,q2t) - alpha*logp_next)."""
+    backup = scale*r + gamma*(1-d)*(min(q1t,q2t) - alpha*logp_next).
+    With importance ``weights`` (prioritized replay) the plain-torch
+    weighted form mean_j w_j (e1_j^2 + e2_j^2)."""
+    if weights is not None:
+        with torch.no_grad():
+            backup = reward_scale * rewards + gamma * (1.0 - done) * (
+                torch.min(q1t, q2t) - alpha * logp_next)
+        w = weights.reshape(q1.shape)     # one weight per row, no broadcast
+        return (w * ((q1 - backup) ** 2 + (q2 - backup) ** 2)).mean()
     if use_native(q1, q2):
         return _NativeQLoss.apply(q1, q2, q1t, q2t, logp_next, rewards,
                                   done, alpha, gamma, reward_scale)
