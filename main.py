@@ -150,6 +150,10 @@ def parse_arguments() -> Namespace:
     parser.add_argument("--per-beta", type=float, default=None,
                         help="Initial importance-weight exponent, annealed "
                              "to 1 over the run (default 0.4)")
+    parser.add_argument("--aug-shift", type=int, default=None,
+                        help="DrQ random-shift augmentation pad in pixels "
+                             "(extension; default 0 = off, or a resumed "
+                             "run's saved value; visual envs only)")
     parser.add_argument("--eval-every", type=int, default=0,
                         help="Deterministic evaluation every N epochs "
                              "(extension; 0 = off)")
@@ -213,6 +217,7 @@ def main():
             per=int(bool(args.per)),
             per_alpha=0.6 if args.per_alpha is None else args.per_alpha,
             per_beta=0.4 if args.per_beta is None else args.per_beta,
+            aug_shift=0 if args.aug_shift is None else args.aug_shift,
         )
         if rank0 and args.logging:
             ckpt.log_params(params)
@@ -232,6 +237,9 @@ def main():
                          ("per_beta", args.per_beta)):
             if val is not None:
                 params[key] = int(val) if key == "per" else val
+        # and the random-shift pad
+        if args.aug_shift is not None:
+            params["aug_shift"] = args.aug_shift
     if args.batch_size is not None:
         params["batch_size"] = args.batch_size
     if args.epochs is not None:

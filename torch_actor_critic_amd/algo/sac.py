@@ -131,6 +131,7 @@ class SAC:
         per_alpha: float = 0.6,
         per_beta: float = 0.4,
         per_eps: float = 1e-6,
+        aug_shift: int = 0,
     ):
         self.alpha = float(alpha)
         self.gamma = float(gamma)
@@ -161,6 +162,14 @@ class SAC:
         self.per_alpha = float(per_alpha)
         self.per_beta = float(per_beta)
         self.per_eps = float(per_eps)
+
+        # DrQ random-shift augmentation of sampled frames (extension; 0 =
+        # off): the visual replay buffer pads by this many pixels and
+        # crops at a random offset, per sample and per frame.  Acting and
+        # evaluation never augment
+        self.aug_shift = int(aug_shift)
+        if self.aug_shift < 0:
+            raise ValueError(f"aug_shift must be >= 0, got {aug_shift}")
 
         # optional learned entropy temperature (default off)
         self.learn_alpha = learn_alpha
@@ -448,6 +457,16 @@ class SAC:
                     f"{type(buffer).__name__} samples uniformly only")
             if not getattr(buffer, "prioritized", False):
                 buffer.set_prioritized(self.per_alpha, self.per_eps)
+
+        # random-shift augmentation: before the update graph is captured,
+        # whose static batch carries the shift tensor
+        if self.aug_shift > 0:
+            if not hasattr(buffer, "set_random_shift"):
+                raise ValueError(
+                    f"aug_shift={self.aug_shift} needs a replay buffer with "
+                    f"set_random_shift(); {type(buffer).__name__} holds no "
+                    "frames")
+            buffer.set_random_shift(self.aug_shift)
 
         # per-rank seeding (reference algorithm.py:203-205)
         seed = 10000 * comm.proc_id()

@@ -26,9 +26,15 @@ class VisualBatch:
     rewards: torch.Tensor
     next_states: MultiObservation
     done: torch.Tensor
+    # random-shift augmentation: int32 [B,4] (dy_s, dx_s, dy_n, dx_n) the
+    # frames of each row were shifted by; None when augmentation is off
+    shifts: t.Optional[torch.Tensor] = None
 
 
 class VisualReplayBuffer:
+    # largest random-shift pad: keeps the 16-bit modulo bias below 0.1%
+    MAX_SHIFT_PAD = 32
+
     def __init__(self, size: int, act_dim: int,
                  device: t.Union[str, torch.device] = "cpu",
                  seed: int = 0, quantize_frames: bool = True):
@@ -50,6 +56,41 @@ class VisualReplayBuffer:
         # device Philox counter for the fused one-kernel gather
         self._philox = torch.zeros(1, dtype=torch.int64, device=dev)
         self._philox_seed = int(seed)
+        # DrQ random-shift augmentation pad (extension; 0 = off)
+        self.shift_pad = 0
+
+    def set_random_shift(self, pad: int) -> None:
+        """DrQ random-shift augmentation of sampled frames: replicate-pad
+        by ``pad`` pixels and crop back at an offset drawn per sample,
+        independently for the state and the next-state frame.  ``0``
+        turns it off.  Stored frames are never changed."""
+        if int(pad) != pad or not 0 <= pad <= self.MAX_SHIFT_PAD:
+            raise ValueError(
+                f"shift pad must be an integer in 0..{self.MAX_SHIFT_PAD}, "
+                f"got {pad!r}")
+        self.shift_pad = int(pad)
+
+    @staticmethod
+    def shift_frames(frames_f32: torch.Tensor, shifts: torch.Tensor,
+                     pad: int) -> torch.Tensor:
+        """The definition of the augmentation.  ``frames_f32 [B,C,H,W]``,
+        ``shifts [B,2]`` integer ``(dy, dx)`` in ``0..2*pad``:
+
+            out[b,c,y,x] = src[b,c, clamp(y+dy-pad, 0, H-1),
+                                    clamp(x+dx-pad, 0, W-1)]
+
+        i.e. replicate-pad by ``pad`` and crop at ``(dy, dx)``;
+        ``(pad, pad)`` is the identity."""
+        B, C, H, W = frames_f32.shape
+        dev = frames_f32.device
+        sh = shifts.to(device=dev, dtype=torch.long).reshape(B, 2)
+        ys = (torch.arange(H, device=dev)[None] + sh[:, :1] - pad)
+        xs = (torch.arange(W, device=dev)[None] + sh[:, 1:] - pad)
+        ys = ys.clamp_(0, H - 1)[:, None, :, None]
+        xs = xs.clamp_(0, W - 1)[:, None, None, :]
+        b = torch.arange(B, device=dev)[:, None, None, None]
+        c = torch.arange(C, device=dev)[None, :, None, None]
+        return frames_f32[b, c, ys, xs]
 
     def _alloc(self, obs: MultiObservation):
         feat_dim = int(obs.features.numel())
@@ -171,9 +212,12 @@ class VisualReplayBuffer:
                 torch.zeros(batch_size, self.feat_dim, **f32),
                 torch.zeros(batch_size, *self.vis_dim, **f32))
 
+        shifts = None
+        if self.shift_pad > 0:
+            shifts = torch.zeros(batch_size, 4, dtype=torch.int32, device=dev)
         return VisualBatch(mo(), torch.zeros(batch_size, self.act_dim, **f32),
                            torch.zeros(batch_size, **f32), mo(),
-                           torch.zeros(batch_size, **f32))
+                           torch.zeros(batch_size, **f32), shifts)
 
     def _native_ext(self):
         if self.device.type != "cuda" or not self._alloc_done:
@@ -183,39 +227,76 @@ class VisualReplayBuffer:
             return require_extension()
         return None
 
+    def sample_at(self, idx: torch.Tensor,
+                  shifts: t.Optional[torch.Tensor] = None) -> VisualBatch:
+        """The batch for given slots and, optionally, given ``[B,4]``
+        shifts ``(dy_s, dx_s, dy_n, dx_n)`` at the current ``shift_pad``
+        (``None`` = unshifted).  The reference the samplers are tested
+        against."""
+        idx = torch.as_tensor(idx, dtype=torch.long, device=self.device)
+        frames = self._dec_frames(self.frames[idx])
+        next_frames = self._dec_frames(self.next_frames[idx])
+        if shifts is not None:
+            shifts = torch.as_tensor(shifts, device=self.device)
+            frames = self.shift_frames(frames, shifts[:, 0:2],
+                                       self.shift_pad)
+            next_frames = self.shift_frames(next_frames, shifts[:, 2:4],
+                                            self.shift_pad)
+        return VisualBatch(
+            MultiObservation(self.features[idx], frames),
+            self.actions[idx], self.rewards[idx],
+            MultiObservation(self.next_features[idx], next_frames),
+            self.done[idx], shifts)
+
     def sample_into(self, out: VisualBatch) -> None:
         """Graph-capturable sampling.  On GPU: ONE fused Philox
         gather+dequantize kernel (replaces ~18 aten index/copy/decode
-        launches per captured update); CPU fallback uses pure tensor
+        launches per captured update), which also applies the random
+        shift when ``shift_pad > 0``; CPU fallback uses pure tensor
         ops (torch RNG is hipGraph-aware)."""
+        pad = self.shift_pad
+        if pad > 0 and out.shifts is None:
+            raise ValueError("random-shift sample_into needs a batch from "
+                             "make_static_batch after set_random_shift()")
         ext = self._native_ext()
         if ext is not None:
-            ext.visual_sample_into(
-                self.features, self.frames, self.next_features,
-                self.next_frames, self.actions, self.rewards, self.done,
-                self._size_dev, self._philox, self._philox_seed,
-                out.states.features, out.states.frame,
-                out.next_states.features, out.next_states.frame,
-                out.actions, out.rewards, out.done)
+            args = (self.features, self.frames, self.next_features,
+                    self.next_frames, self.actions, self.rewards, self.done,
+                    self._size_dev, self._philox, self._philox_seed,
+                    out.states.features, out.states.frame,
+                    out.next_states.features, out.next_states.frame,
+                    out.actions, out.rewards, out.done)
+            if pad > 0:
+                ext.visual_sample_into_shift(
+                    *args, pad, self.vis_dim[-2], self.vis_dim[-1],
+                    out.shifts)
+            else:
+                ext.visual_sample_into(*args)
             return
         B = out.actions.shape[0]
         u = torch.rand(B, device=self.device)
         size = self._size_dev.clamp(min=1).to(torch.float32)
         idx = (u * size).long().clamp_(max=self.max_size - 1)
-        out.states.features.copy_(self.features[idx])
-        out.states.frame.copy_(self._dec_frames(self.frames[idx]))
-        out.next_states.features.copy_(self.next_features[idx])
-        out.next_states.frame.copy_(self._dec_frames(self.next_frames[idx]))
-        out.actions.copy_(self.actions[idx])
-        out.rewards.copy_(self.rewards[idx])
-        out.done.copy_(self.done[idx])
+        shifts = None
+        if pad > 0:
+            out.shifts.copy_(torch.randint(0, 2 * pad + 1, (B, 4),
+                                           device=self.device))
+            shifts = out.shifts
+        b = self.sample_at(idx, shifts)
+        out.states.features.copy_(b.states.features)
+        out.states.frame.copy_(b.states.frame)
+        out.next_states.features.copy_(b.next_states.features)
+        out.next_states.frame.copy_(b.next_states.frame)
+        out.actions.copy_(b.actions)
+        out.rewards.copy_(b.rewards)
+        out.done.copy_(b.done)
 
     def sample(self, batch_size: int) -> VisualBatch:
         idx_np = self._rng.choice(self.size, size=batch_size, replace=False)
-        idx = torch.as_tensor(idx_np, dtype=torch.long, device=self.device)
-        state = MultiObservation(self.features[idx],
-                                 self._dec_frames(self.frames[idx]))
-        next_state = MultiObservation(self.next_features[idx],
-                                      self._dec_frames(self.next_frames[idx]))
-        return VisualBatch(state, self.actions[idx], self.rewards[idx],
-                           next_state, self.done[idx])
+        shifts = None
+        if self.shift_pad > 0:
+            shifts = torch.as_tensor(
+                self._rng.integers(0, 2 * self.shift_pad + 1,
+                                   size=(batch_size, 4)).astype(np.int32))
+        return self.sample_at(torch.as_tensor(idx_np, dtype=torch.long),
+                              shifts)

@@ -1023,6 +1023,127 @@ void visual_gather_kernel(const float* __restrict__ feat,
 }
 
 // ---------------------------------------------------------------------------
+// Visual replay gather with DrQ random-shift augmentation: the same draw
+// and field copies as visual_gather_kernel, but each frame is read through
+//   out[c, y, x] = src[c, clamp(y + dy - p, 0, H-1), clamp(x + dx - p, 0, W-1)]
+// (replicate-pad by p, crop at (dy, dx)).  The two shifts come from the two
+// Philox words the plain kernel leaves unused: r.z for the state frame,
+// r.w for the next-state frame, 16 bits per axis, mod (2p+1).
+// ---------------------------------------------------------------------------
+
+template <bool QUANT>
+DEVINL float frame_px(const void* __restrict__ p, int64_t i) {
+  if constexpr (QUANT)
+    return (float)((const uint8_t*)p)[i] / 127.5f - 1.0f;
+  else
+    return ((const float*)p)[i];
+}
+
+template <bool QUANT, bool VEC>
+__global__ __launch_bounds__(256)
+void visual_gather_shift_kernel(const float* __restrict__ feat,
+                                const void* __restrict__ frames,
+                                const float* __restrict__ nfeat,
+                                const void* __restrict__ nframes,
+                                const float* __restrict__ act,
+                                const float* __restrict__ rew,
+                                const float* __restrict__ done,
+                                const int64_t* __restrict__ size_dev,
+                                const int64_t* __restrict__ ctr,
+                                uint64_t seed,
+                                float* __restrict__ of,
+                                float* __restrict__ ofr,
+                                float* __restrict__ onf,
+                                float* __restrict__ onfr,
+                                float* __restrict__ oa,
+                                float* __restrict__ orew,
+                                float* __restrict__ od,
+                                int32_t* __restrict__ oshift,
+                                int feat_dim, int act_dim, int pad,
+                                int rows, int H, int W) {
+  // grid (B, SLICES) as in visual_gather_kernel; blockIdx.y partitions the
+  // rows = C*H image rows of the frame pair
+  const int j = blockIdx.x;
+  const int slice = blockIdx.y;
+  const int nslice = gridDim.y;
+  const uint64_t size = (uint64_t)size_dev[0];
+  Philox4 r = philox4(seed, (uint64_t)ctr[0], (uint64_t)j);
+  uint64_t u = ((uint64_t)r.x << 32) | r.y;
+  const int64_t idx = (int64_t)(u % (size ? size : 1));
+  const uint32_t span = 2u * (uint32_t)pad + 1u;
+  const int dy0 = (int)((r.z >> 16) % span) - pad;
+  const int dx0 = (int)((r.z & 0xffffu) % span) - pad;
+  const int dy1 = (int)((r.w >> 16) % span) - pad;
+  const int dx1 = (int)((r.w & 0xffffu) % span) - pad;
+
+  if (slice == 0) {
+    for (int c = threadIdx.x; c < feat_dim; c += blockDim.x) {
+      of[(int64_t)j * feat_dim + c] = feat[idx * feat_dim + c];
+      onf[(int64_t)j * feat_dim + c] = nfeat[idx * feat_dim + c];
+    }
+    for (int c = threadIdx.x; c < act_dim; c += blockDim.x)
+      oa[(int64_t)j * act_dim + c] = act[idx * act_dim + c];
+    if (threadIdx.x == 0) {
+      orew[j] = rew[idx];
+      od[j] = done[idx];
+      oshift[4 * j + 0] = dy0 + pad;
+      oshift[4 * j + 1] = dx0 + pad;
+      oshift[4 * j + 2] = dy1 + pad;
+      oshift[4 * j + 3] = dx1 + pad;
+    }
+  }
+
+  // work item = 4 consecutive x of one (c, y) row, items of a row and of
+  // consecutive rows on consecutive lanes: the clamped source row is
+  // computed once per item and the 16-byte stores of a wave are contiguous
+  const int64_t frame_n = (int64_t)rows * W;
+  const int xg = (W + 3) >> 2;
+  const int rchunk = (rows + nslice - 1) / nslice;
+  const int r_lo = slice * rchunk;
+  const int r_hi = min(rows, r_lo + rchunk);
+  const int items = max(0, r_hi - r_lo) * xg;
+  const int64_t src_off = idx * frame_n;
+  float* __restrict__ o0 = ofr + (int64_t)j * frame_n;
+  float* __restrict__ o1 = onfr + (int64_t)j * frame_n;
+  for (int i = threadIdx.x; i < items; i += blockDim.x) {
+    const int rl = i / xg;
+    const int x = (i - rl * xg) << 2;
+    const int row = r_lo + rl;        // c * H + y
+    const int c = row / H;
+    const int y = row - c * H;
+    const int sy0 = min(max(y + dy0, 0), H - 1);
+    const int sy1 = min(max(y + dy1, 0), H - 1);
+    const int64_t b0 = src_off + (int64_t)(c * H + sy0) * W;
+    const int64_t b1 = src_off + (int64_t)(c * H + sy1) * W;
+    float v0[4], v1[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      // x + k may pass W - 1 in the scalar tail; the clamp keeps the read
+      // inside the row and the value is not stored
+      const int sx0 = min(max(x + k + dx0, 0), W - 1);
+      const int sx1 = min(max(x + k + dx1, 0), W - 1);
+      v0[k] = frame_px<QUANT>(frames, b0 + sx0);
+      v1[k] = frame_px<QUANT>(nframes, b1 + sx1);
+    }
+    const int64_t o = (int64_t)row * W + x;
+    if constexpr (VEC) {
+      *reinterpret_cast<float4*>(o0 + o) =
+          make_float4(v0[0], v0[1], v0[2], v0[3]);
+      *reinterpret_cast<float4*>(o1 + o) =
+          make_float4(v1[0], v1[1], v1[2], v1[3]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (x + k < W) {
+          o0[o + k] = v0[k];
+          o1[o + k] = v1[k];
+        }
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Philox standard-normal sampler (Box-Muller) — graph-replay-safe noise
 // for the reparameterized policy sample (torch's RNG offset is host-side;
 // this keeps the whole SAC update replayable with fresh noise).
@@ -1576,6 +1697,73 @@ void visual_sample_into(torch::Tensor feat, torch::Tensor frames,
                        od.data_ptr<float>(), feat_dim, frame_n, act_dim);
 }
 
+void visual_sample_into_shift(torch::Tensor feat, torch::Tensor frames,
+                              torch::Tensor nfeat, torch::Tensor nframes,
+                              torch::Tensor act, torch::Tensor rew,
+                              torch::Tensor done, torch::Tensor size_dev,
+                              torch::Tensor ctr, int64_t seed,
+                              torch::Tensor of, torch::Tensor ofr,
+                              torch::Tensor onf, torch::Tensor onfr,
+                              torch::Tensor oa, torch::Tensor orew,
+                              torch::Tensor od, int64_t pad, int64_t H,
+                              int64_t W, torch::Tensor shifts) {
+  CHECK_IN(feat); CHECK_IN(of); CHECK_IN(ofr); CHECK_IN(onfr);
+  TORCH_CHECK(pad >= 1 && pad <= 32, "shift pad must be in 1..32");
+  const int B = (int)of.size(0);
+  const int feat_dim = (int)feat.size(1);
+  const int act_dim = (int)act.size(1);
+  const int64_t frame_n = frames.numel() / frames.size(0);
+  TORCH_CHECK(H >= 1 && W >= 1 && frame_n % (H * W) == 0 &&
+              frame_n < ((int64_t)1 << 31),
+              "frame size is not a multiple of H*W");
+  TORCH_CHECK(frames.is_cuda() && frames.is_contiguous() &&
+              nframes.is_cuda() && nframes.is_contiguous() &&
+              nframes.scalar_type() == frames.scalar_type() &&
+              nframes.numel() == frames.numel(), "bad frame storage");
+  TORCH_CHECK(ofr.numel() == (int64_t)B * frame_n &&
+              onfr.numel() == (int64_t)B * frame_n,
+              "batch frames do not match the stored frame size");
+  TORCH_CHECK(of.numel() == (int64_t)B * feat_dim &&
+              onf.numel() == (int64_t)B * feat_dim &&
+              oa.numel() == (int64_t)B * act_dim && orew.numel() == B &&
+              od.numel() == B, "batch fields do not match the batch size");
+  TORCH_CHECK(shifts.is_cuda() && shifts.is_contiguous() &&
+              shifts.scalar_type() == torch::kInt32 &&
+              shifts.numel() == (int64_t)B * 4,
+              "shifts must be an int32 [B,4] device tensor");
+  const bool quant = frames.scalar_type() == torch::kUInt8;
+  TORCH_CHECK(quant || frames.scalar_type() == torch::kFloat32,
+              "frames must be uint8 or float32");
+  const int rows = (int)(frame_n / W);
+  // one 16-byte store per 4 pixels needs rows and both bases 16-B aligned
+  const bool vec = W % 4 == 0 &&
+      (reinterpret_cast<uintptr_t>(ofr.data_ptr<float>()) |
+       reinterpret_cast<uintptr_t>(onfr.data_ptr<float>())) % 16 == 0;
+  auto s = cur_stream();
+  hipLaunchKernelGGL(bump_counter_kernel, dim3(1), dim3(1), 0, s,
+                     ctr.data_ptr<int64_t>());
+  const int slices = (int)std::min<int64_t>(8, (frame_n + 4095) / 4096);
+  dim3 grid(B, std::max(1, slices));
+  auto L = [&](auto q, auto v) {
+    hipLaunchKernelGGL(
+        (visual_gather_shift_kernel<decltype(q)::value, decltype(v)::value>),
+        grid, dim3(256), 0, s, feat.data_ptr<float>(), frames.data_ptr(),
+        nfeat.data_ptr<float>(), nframes.data_ptr(),
+        act.data_ptr<float>(), rew.data_ptr<float>(),
+        done.data_ptr<float>(), size_dev.data_ptr<int64_t>(),
+        ctr.data_ptr<int64_t>(), (uint64_t)seed, of.data_ptr<float>(),
+        ofr.data_ptr<float>(), onf.data_ptr<float>(),
+        onfr.data_ptr<float>(), oa.data_ptr<float>(),
+        orew.data_ptr<float>(), od.data_ptr<float>(),
+        shifts.data_ptr<int32_t>(), feat_dim, act_dim, (int)pad, rows,
+        (int)H, (int)W);
+  };
+  if (quant && vec) L(std::true_type{}, std::true_type{});
+  else if (quant) L(std::true_type{}, std::false_type{});
+  else if (vec) L(std::false_type{}, std::true_type{});
+  else L(std::false_type{}, std::false_type{});
+}
+
 void bump_counter(torch::Tensor ctr) {
   hipLaunchKernelGGL(bump_counter_kernel, dim3(1), dim3(1), 0, cur_stream(),
                      ctr.data_ptr<int64_t>());
@@ -1682,6 +1870,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("per_sample", &per_sample,
         "sum-tree draw only: (slot, probability, target u)");
   m.def("visual_sample_into", &visual_sample_into);
+  m.def("visual_sample_into_shift", &visual_sample_into_shift,
+        "visual_sample_into with DrQ random-shift augmentation");
   m.def("visual_store_into", &visual_store_into);
   m.def("philox_randn_", &philox_randn_);
   m.def("bump_counter", &bump_counter);
