@@ -140,7 +140,7 @@ def parse_arguments() -> Namespace:
     parser.add_argument("--n-step", type=int, default=None,
                         help="N-step returns in the Bellman backup "
                              "(extension; default 1, or a resumed run's "
-                             "saved value; vector-observation envs only)")
+                             "saved value; vector and visual envs)")
     parser.add_argument("--per", action="store_true", default=None,
                         help="Prioritized experience replay (extension; "
                              "default off, or a resumed run's saved value; "

@@ -8,8 +8,12 @@ a synchronised loop) and a captured graph of GRAPH_CALLS calls, which is
 how the update engine runs it and takes the launch cost out.
 
     python scripts/visual_gather_micro.py [--plain-only] [--rounds N]
+                                          [--n-step N]
 
 ``--plain-only`` is for commits from before the random shift existed.
+``--n-step N`` (N > 1) adds the n-step gather, unshifted and shifted, on
+the same buffer; episodes end every EPISODE slots, so all but a few
+windows are N slots long.
 """
 import argparse
 import os
@@ -31,16 +35,21 @@ parser = argparse.ArgumentParser()
 parser.add_argument("--plain-only", action="store_true")
 parser.add_argument("--rounds", type=int, default=7)
 parser.add_argument("--pad", type=int, default=4)
+parser.add_argument("--n-step", type=int, default=1)
 args = parser.parse_args()
 
 dev = torch.device("cuda:0")
 require_extension()
 B, SLOTS, FEAT, ACT = 64, 8192, 17, 6
 EAGER_CALLS, GRAPH_CALLS, GRAPH_REPLAYS = 2000, 32, 100
+EPISODE = 500
 
 
 def make_buffer(vis):
     buf = VisualReplayBuffer(SLOTS, ACT, device=dev, seed=1)
+    if args.n_step > 1:
+        buf.set_n_step(args.n_step, 0.99)
+        buf.episode_end[EPISODE - 1::EPISODE] = 1.0
     mo = MultiObservation(torch.zeros(FEAT, device=dev),
                           torch.zeros(*vis, device=dev))
     buf.store(mo, np.zeros(ACT, dtype=np.float32), 0.0, mo, 0.0)
@@ -51,7 +60,16 @@ def make_buffer(vis):
     buf.size = SLOTS
     buf.ptr = 0
     buf._size_dev.fill_(SLOTS)
+    if args.n_step > 1:
+        buf._ptr_dev.fill_(0)
     return buf
+
+
+def select(buf, n_step, pad):
+    if not args.plain_only:
+        buf.set_random_shift(pad)
+    if args.n_step > 1:
+        buf.set_n_step(n_step, 0.99)
 
 
 def eager_us(buf, out):
@@ -96,23 +114,28 @@ def report(name, xs):
 
 for vis in ((3, 64, 64), (3, 84, 84)):
     buf = make_buffer(vis)
-    variants = {"plain": 0} if args.plain_only \
-        else {"plain": 0, f"shift p={args.pad}": args.pad}
+    # name -> (n_step, pad)
+    variants = {"plain": (1, 0)}
+    if not args.plain_only:
+        variants[f"shift p={args.pad}"] = (1, args.pad)
+    if args.n_step > 1:
+        variants[f"n={args.n_step} plain"] = (args.n_step, 0)
+        if not args.plain_only:
+            variants[f"n={args.n_step} shift p={args.pad}"] = \
+                (args.n_step, args.pad)
     outs, graphs = {}, {}
-    for name, pad in variants.items():
-        if pad:
-            buf.set_random_shift(pad)
+    for name, (n_step, pad) in variants.items():
+        select(buf, n_step, pad)
         outs[name] = buf.make_static_batch(B)
         graphs[name] = capture(buf, outs[name])
     times = {(n, k): [] for n in variants for k in ("eager", "graph")}
     for _ in range(args.rounds):
-        for name, pad in variants.items():
-            if not args.plain_only:
-                buf.set_random_shift(pad)
+        for name, (n_step, pad) in variants.items():
+            select(buf, n_step, pad)
             times[name, "eager"].append(eager_us(buf, outs[name]))
             times[name, "graph"].append(graph_us(graphs[name]))
     n = int(np.prod(vis))
     moved = B * 2 * n * (1 + 4)       # u8 read + f32 write, both frames
     print(f"visual gather B={B} frame={vis} u8: {moved / 1e6:.2f} MB/call")
     for (name, kind), xs in times.items():
-        report(f"{name:10s} {kind} per call", xs)
+        report(f"{name:16s} {kind} per call", xs)

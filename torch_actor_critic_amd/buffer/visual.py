@@ -8,6 +8,13 @@ features and frames as two dense tensors per side:
 ``features [N, F]`` fp32 and ``frames [N, C, H, W]`` — frames optionally
 uint8-quantized (scale [-1,1] -> u8) to fit 1M 3x64x64 transitions in
 ~25 GB of the 288 GB HBM3E instead of ~98 GB fp32.
+
+Optional n-step returns (extension, default off), as in ``ReplayBuffer``:
+after ``set_n_step(n, gamma)`` every sampler returns the discounted n-step
+reward sum, the features and frame of the window's last slot as the next
+state and an *effective* done (``sample_at`` is the executable definition).
+It composes with the random shift: the state shift applies to the sampled
+slot's frame, the next-state shift to the last slot's next frame.
 """
 
 import typing as t
@@ -21,6 +28,9 @@ from ..envs.visual import MultiObservation
 
 @dataclass(frozen=True)
 class VisualBatch:
+    """With n-step sampling ``rewards``, ``next_states`` and ``done`` are
+    the window's discounted sum, last next state and effective done, as in
+    ``buffer.replay.Batch``."""
     states: MultiObservation
     actions: torch.Tensor
     rewards: torch.Tensor
@@ -34,6 +44,7 @@ class VisualBatch:
 class VisualReplayBuffer:
     # largest random-shift pad: keeps the 16-bit modulo bias below 0.1%
     MAX_SHIFT_PAD = 32
+    MAX_N_STEP = 64   # one wave64 lane per window slot in the gather kernel
 
     def __init__(self, size: int, act_dim: int,
                  device: t.Union[str, torch.device] = "cpu",
@@ -58,6 +69,37 @@ class VisualReplayBuffer:
         self._philox_seed = int(seed)
         # DrQ random-shift augmentation pad (extension; 0 = off)
         self.shift_pad = 0
+        # n-step returns (set_n_step): off by default — nothing below is
+        # allocated, copied or launched while n_step == 1
+        self.n_step = 1
+        self.gamma = 1.0
+        self.episode_end: t.Optional[torch.Tensor] = None
+        self._ptr_dev: t.Optional[torch.Tensor] = None
+
+    def set_n_step(self, n: int, gamma: float) -> None:
+        """Sample n-step returns with discount ``gamma`` from now on.
+        For n > 1 the ring gains an ``episode_end`` field (1 where an
+        episode ended after the transition for ANY reason, truncation
+        included) and a device mirror of the write head, so the buffer
+        must still be empty; neither depends on the observation shape, so
+        this works before the first ``store``."""
+        n = int(n)
+        if not 1 <= n <= self.MAX_N_STEP:
+            raise ValueError(
+                f"n_step must be in 1..{self.MAX_N_STEP}, got {n}")
+        if n > 1 and self.episode_end is None:
+            if self.size != 0:
+                raise ValueError(
+                    "set_n_step(n > 1) needs an empty buffer: transitions "
+                    "stored so far carry no episode boundaries")
+            self.episode_end = torch.zeros(self.max_size,
+                                           dtype=torch.float32,
+                                           device=self.device)
+            self._ptr_dev = torch.zeros(1, dtype=torch.int64,
+                                        device=self.device)
+            self._ptr_dev.fill_(self.ptr)
+        self.n_step = n
+        self.gamma = float(gamma)
 
     def set_random_shift(self, pad: int) -> None:
         """DrQ random-shift augmentation of sampled frames: replicate-pad
@@ -117,12 +159,16 @@ class VisualReplayBuffer:
         return frames.to(torch.float32) / 127.5 - 1.0
 
     def store(self, obs: MultiObservation, act, rew,
-              next_obs: MultiObservation, done):
+              next_obs: MultiObservation, done, end=None):
+        """``end`` (default: ``done``) marks the last transition of an
+        episode, whatever ended it; only n-step sampling reads it."""
         if not self._alloc_done:
             self._alloc(obs)
+        end = float(done if end is None else end)
         ext = self._native_ext()
         if ext is not None:
-            self._store_fast(ext, obs, act, rew, next_obs, done)
+            # the n-step store kernel also writes episode_end and _ptr_dev
+            self._store_fast(ext, obs, act, rew, next_obs, done, end)
         else:
             i = self.ptr
             self.features[i] = obs.features.reshape(-1).to(self.device)
@@ -136,11 +182,14 @@ class VisualReplayBuffer:
             ).reshape(self.act_dim)
             self.rewards[i] = float(rew)
             self.done[i] = float(done)
+            if self.episode_end is not None:
+                self.episode_end[i] = end
+                self._ptr_dev.fill_((i + 1) % self.max_size)
         self.ptr = (self.ptr + 1) % self.max_size
         self.size = min(self.size + 1, self.max_size)
         self._size_dev.fill_(self.size)
 
-    def _store_fast(self, ext, obs, act, rew, next_obs, done):
+    def _store_fast(self, ext, obs, act, rew, next_obs, done, end):
         """GPU store: stage the transition through pinned buffers and run
         ONE fused quantize+write kernel (the eager path costs ~10 aten
         copies plus a CPU-side u8 encode chain per env step)."""
@@ -194,6 +243,15 @@ class VisualReplayBuffer:
             st[d].copy_(st[p], non_blocking=True)
         self._h2d_done.record()
         self._last_next_src = (next_obs.features, next_obs.frame)
+        if self.episode_end is not None:
+            ext.visual_store_into_n(st["f"], st["F"], st["nf"], st["nF"],
+                                    st["a"], float(rew), float(done), end,
+                                    self.features, self.frames,
+                                    self.next_features, self.next_frames,
+                                    self.actions, self.rewards, self.done,
+                                    self.episode_end, self._ptr_dev,
+                                    self.ptr)
+            return
         ext.visual_store_into(st["f"], st["F"], st["nf"], st["nF"],
                               st["a"], float(rew), float(done),
                               self.features, self.frames,
@@ -227,15 +285,58 @@ class VisualReplayBuffer:
             return require_extension()
         return None
 
+    def _nstep_window(self, idx: torch.Tensor, n: int):
+        """(last slot, reward sum, effective done) of the n-step windows
+        that start at ``idx``; see ``sample_at``."""
+        S = self.max_size
+        newest = (self.ptr - 1) % S if self.size else 0
+        gamma = torch.tensor(self.gamma, dtype=torch.float32,
+                             device=self.device)
+        R = torch.zeros(idx.shape, dtype=torch.float32, device=self.device)
+        disc = torch.ones_like(R)
+        last = idx.clone()
+        active = torch.ones(idx.shape, dtype=torch.bool, device=self.device)
+        for m in range(n):
+            j = (idx + m) % S
+            R = torch.where(active, R + disc * self.rewards[j], R)
+            last = torch.where(active, j, last)
+            stop = ((self.done[j] != 0) | (self.episode_end[j] != 0)
+                    | (j == newest))
+            active = active & ~stop
+            if m + 1 < n:
+                disc = torch.where(active, disc * gamma, disc)
+        return last, R, 1.0 - disc * (1.0 - self.done[last])
+
     def sample_at(self, idx: torch.Tensor,
-                  shifts: t.Optional[torch.Tensor] = None) -> VisualBatch:
+                  shifts: t.Optional[torch.Tensor] = None,
+                  n_step: t.Optional[int] = None) -> VisualBatch:
         """The batch for given slots and, optionally, given ``[B,4]``
         shifts ``(dy_s, dx_s, dy_n, dx_n)`` at the current ``shift_pad``
         (``None`` = unshifted).  The reference the samplers are tested
-        against."""
+        against.
+
+        ``n_step`` (default: the buffer's) > 1 gives n-step returns by the
+        window rule of ``ReplayBuffer.sample_at``: from slot i the window
+        walks j = i, i+1, ... (mod max_size), adding ``gamma^m *
+        rewards[j]`` in fp32 in this order (gamma^m by repeated fp32
+        multiply), and closes at the first j with ``done[j]`` or
+        ``episode_end[j]`` set, at the newest slot (the walk never crosses
+        the write head) or after n slots.  With M slots walked and
+        ``last`` the final one: state features, state frame and action
+        come from slot i, next features and next frame from slot
+        ``last``, reward is the sum and done is ``1 - gamma^(M-1) *
+        (1 - done[last])``.  The state shift then applies to the frame of
+        slot i, the next-state shift to the next frame of slot ``last``."""
+        n = self.n_step if n_step is None else int(n_step)
         idx = torch.as_tensor(idx, dtype=torch.long, device=self.device)
+        last, rewards, done = idx, self.rewards[idx], self.done[idx]
+        if n > 1:
+            if self.episode_end is None:
+                raise ValueError("n-step sampling needs set_n_step(n > 1) "
+                                 "before the first store")
+            last, rewards, done = self._nstep_window(idx, n)
         frames = self._dec_frames(self.frames[idx])
-        next_frames = self._dec_frames(self.next_frames[idx])
+        next_frames = self._dec_frames(self.next_frames[last])
         if shifts is not None:
             shifts = torch.as_tensor(shifts, device=self.device)
             frames = self.shift_frames(frames, shifts[:, 0:2],
@@ -244,21 +345,33 @@ class VisualReplayBuffer:
                                             self.shift_pad)
         return VisualBatch(
             MultiObservation(self.features[idx], frames),
-            self.actions[idx], self.rewards[idx],
-            MultiObservation(self.next_features[idx], next_frames),
-            self.done[idx], shifts)
+            self.actions[idx], rewards,
+            MultiObservation(self.next_features[last], next_frames),
+            done, shifts)
 
     def sample_into(self, out: VisualBatch) -> None:
         """Graph-capturable sampling.  On GPU: ONE fused Philox
         gather+dequantize kernel (replaces ~18 aten index/copy/decode
         launches per captured update), which also applies the random
-        shift when ``shift_pad > 0``; CPU fallback uses pure tensor
-        ops (torch RNG is hipGraph-aware)."""
+        shift when ``shift_pad > 0`` and walks the n-step window when
+        ``n_step > 1``; CPU fallback uses pure tensor ops (torch RNG is
+        hipGraph-aware)."""
         pad = self.shift_pad
         if pad > 0 and out.shifts is None:
             raise ValueError("random-shift sample_into needs a batch from "
                              "make_static_batch after set_random_shift()")
         ext = self._native_ext()
+        if ext is not None and self.n_step > 1:
+            ext.visual_sample_into_n(
+                self.features, self.frames, self.next_features,
+                self.next_frames, self.actions, self.rewards, self.done,
+                self.episode_end, self._size_dev, self._ptr_dev,
+                self._philox, self._philox_seed, self.n_step, self.gamma,
+                out.states.features, out.states.frame,
+                out.next_states.features, out.next_states.frame,
+                out.actions, out.rewards, out.done, pad, self.vis_dim[-2],
+                self.vis_dim[-1], out.shifts if pad > 0 else None)
+            return
         if ext is not None:
             args = (self.features, self.frames, self.next_features,
                     self.next_frames, self.actions, self.rewards, self.done,

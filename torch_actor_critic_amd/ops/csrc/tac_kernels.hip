@@ -1039,6 +1039,58 @@ DEVINL float frame_px(const void* __restrict__ p, int64_t i) {
     return ((const float*)p)[i];
 }
 
+// One block's share of a shifted frame pair: the image rows
+// [r_lo, r_lo + items / xg) of the state frame at frames + off0 and of the
+// next-state frame at nframes + off1 (element offsets), read through their
+// shifts and written to o0 / o1.  Work item = 4 consecutive x of one
+// (c, y) row, items of a row and of consecutive rows on consecutive lanes:
+// the clamped source row is computed once per item and the 16-byte stores
+// of a wave are contiguous.
+template <bool QUANT, bool VEC>
+DEVINL void shift_copy_pair(const void* __restrict__ frames,
+                            const void* __restrict__ nframes,
+                            int64_t off0, int64_t off1,
+                            float* __restrict__ o0, float* __restrict__ o1,
+                            int dy0, int dx0, int dy1, int dx1,
+                            int r_lo, int items, int xg, int H, int W) {
+  for (int i = threadIdx.x; i < items; i += blockDim.x) {
+    const int rl = i / xg;
+    const int x = (i - rl * xg) << 2;
+    const int row = r_lo + rl;        // c * H + y
+    const int c = row / H;
+    const int y = row - c * H;
+    const int sy0 = min(max(y + dy0, 0), H - 1);
+    const int sy1 = min(max(y + dy1, 0), H - 1);
+    const int64_t b0 = off0 + (int64_t)(c * H + sy0) * W;
+    const int64_t b1 = off1 + (int64_t)(c * H + sy1) * W;
+    float v0[4], v1[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      // x + k may pass W - 1 in the scalar tail; the clamp keeps the read
+      // inside the row and the value is not stored
+      const int sx0 = min(max(x + k + dx0, 0), W - 1);
+      const int sx1 = min(max(x + k + dx1, 0), W - 1);
+      v0[k] = frame_px<QUANT>(frames, b0 + sx0);
+      v1[k] = frame_px<QUANT>(nframes, b1 + sx1);
+    }
+    const int64_t o = (int64_t)row * W + x;
+    if constexpr (VEC) {
+      *reinterpret_cast<float4*>(o0 + o) =
+          make_float4(v0[0], v0[1], v0[2], v0[3]);
+      *reinterpret_cast<float4*>(o1 + o) =
+          make_float4(v1[0], v1[1], v1[2], v1[3]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (x + k < W) {
+          o0[o + k] = v0[k];
+          o1[o + k] = v1[k];
+        }
+      }
+    }
+  }
+}
+
 template <bool QUANT, bool VEC>
 __global__ __launch_bounds__(256)
 void visual_gather_shift_kernel(const float* __restrict__ feat,
@@ -1093,9 +1145,6 @@ void visual_gather_shift_kernel(const float* __restrict__ feat,
     }
   }
 
-  // work item = 4 consecutive x of one (c, y) row, items of a row and of
-  // consecutive rows on consecutive lanes: the clamped source row is
-  // computed once per item and the 16-byte stores of a wave are contiguous
   const int64_t frame_n = (int64_t)rows * W;
   const int xg = (W + 3) >> 2;
   const int rchunk = (rows + nslice - 1) / nslice;
@@ -1103,44 +1152,115 @@ void visual_gather_shift_kernel(const float* __restrict__ feat,
   const int r_hi = min(rows, r_lo + rchunk);
   const int items = max(0, r_hi - r_lo) * xg;
   const int64_t src_off = idx * frame_n;
-  float* __restrict__ o0 = ofr + (int64_t)j * frame_n;
-  float* __restrict__ o1 = onfr + (int64_t)j * frame_n;
-  for (int i = threadIdx.x; i < items; i += blockDim.x) {
-    const int rl = i / xg;
-    const int x = (i - rl * xg) << 2;
-    const int row = r_lo + rl;        // c * H + y
-    const int c = row / H;
-    const int y = row - c * H;
-    const int sy0 = min(max(y + dy0, 0), H - 1);
-    const int sy1 = min(max(y + dy1, 0), H - 1);
-    const int64_t b0 = src_off + (int64_t)(c * H + sy0) * W;
-    const int64_t b1 = src_off + (int64_t)(c * H + sy1) * W;
-    float v0[4], v1[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      // x + k may pass W - 1 in the scalar tail; the clamp keeps the read
-      // inside the row and the value is not stored
-      const int sx0 = min(max(x + k + dx0, 0), W - 1);
-      const int sx1 = min(max(x + k + dx1, 0), W - 1);
-      v0[k] = frame_px<QUANT>(frames, b0 + sx0);
-      v1[k] = frame_px<QUANT>(nframes, b1 + sx1);
-    }
-    const int64_t o = (int64_t)row * W + x;
-    if constexpr (VEC) {
-      *reinterpret_cast<float4*>(o0 + o) =
-          make_float4(v0[0], v0[1], v0[2], v0[3]);
-      *reinterpret_cast<float4*>(o1 + o) =
-          make_float4(v1[0], v1[1], v1[2], v1[3]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        if (x + k < W) {
-          o0[o + k] = v0[k];
-          o1[o + k] = v1[k];
+  shift_copy_pair<QUANT, VEC>(frames, nframes, src_off, src_off,
+                              ofr + (int64_t)j * frame_n,
+                              onfr + (int64_t)j * frame_n, dy0, dx0, dy1, dx1,
+                              r_lo, items, xg, H, W);
+}
+
+// ---------------------------------------------------------------------------
+// N-step visual replay gather (buffer/visual.py::sample_at is the executable
+// definition): the draw of visual_gather_kernel / visual_gather_shift_kernel
+// (same slot for the same (seed, counter, j), same r.z / r.w shifts), the
+// window of nstep_walk.  State features, state frame and action come from
+// the drawn slot, next features and next frame from the window's last
+// slot, reward and done are the window's.  pad == 0 is the unshifted
+// gather: span is 1, every shift is 0 and oshift is not written.
+// ---------------------------------------------------------------------------
+
+template <bool QUANT, bool VEC>
+__global__ __launch_bounds__(256)
+void visual_gather_n_kernel(const float* __restrict__ feat,
+                            const void* __restrict__ frames,
+                            const float* __restrict__ nfeat,
+                            const void* __restrict__ nframes,
+                            const float* __restrict__ act,
+                            const float* __restrict__ rew,
+                            const float* __restrict__ done,
+                            const float* __restrict__ ep_end,
+                            const int64_t* __restrict__ size_dev,
+                            const int64_t* __restrict__ ptr_dev,
+                            const int64_t* __restrict__ ctr,
+                            uint64_t seed,
+                            float* __restrict__ of,
+                            float* __restrict__ ofr,
+                            float* __restrict__ onf,
+                            float* __restrict__ onfr,
+                            float* __restrict__ oa,
+                            float* __restrict__ orew,
+                            float* __restrict__ od,
+                            int32_t* __restrict__ oshift,
+                            int feat_dim, int act_dim, int pad,
+                            int rows, int H, int W, int64_t cap, int n,
+                            float gamma) {
+  // grid (B, SLICES) as in the 1-step kernels.  Every block needs the
+  // window's last slot for its share of the next frame, so wave 0 of every
+  // block walks the window (one load latency; redundant across the <= 8
+  // slices, which is cheaper than a second launch or a global hand-off)
+  // and hands it over through LDS; only slice 0 writes the per-row fields.
+  // Both frames are then copied in one loop after the barrier: copying
+  // the state frame before it, to hide the walk, halves the loads in
+  // flight per thread and measured 1.4-2 us slower.
+  __shared__ int64_t s_last;
+  const int j = blockIdx.x;
+  const int slice = blockIdx.y;
+  const int nslice = gridDim.y;
+  const uint64_t size = (uint64_t)size_dev[0];
+  Philox4 r = philox4(seed, (uint64_t)ctr[0], (uint64_t)j);
+  uint64_t u = ((uint64_t)r.x << 32) | r.y;
+  const int64_t idx = (int64_t)(u % (size ? size : 1));
+  const uint32_t span = 2u * (uint32_t)pad + 1u;
+  const int dy0 = (int)((r.z >> 16) % span) - pad;
+  const int dx0 = (int)((r.z & 0xffffu) % span) - pad;
+  const int dy1 = (int)((r.w >> 16) % span) - pad;
+  const int dx1 = (int)((r.w & 0xffffu) % span) - pad;
+
+  if (threadIdx.x < WAVE) {
+    // with size == 0 slot 0 counts as the newest: the window is slot 0
+    const int64_t newest = size ? (ptr_dev[0] + cap - 1) % cap : 0;
+    float R, de;
+    const int64_t last = nstep_walk(rew, done, ep_end, idx, cap, newest, n,
+                                    gamma, &R, &de);
+    if (threadIdx.x == 0) {
+      s_last = last;
+      if (slice == 0) {
+        orew[j] = R;
+        od[j] = de;
+        if (oshift != nullptr) {
+          oshift[4 * j + 0] = dy0 + pad;
+          oshift[4 * j + 1] = dx0 + pad;
+          oshift[4 * j + 2] = dy1 + pad;
+          oshift[4 * j + 3] = dx1 + pad;
         }
       }
     }
   }
+  if (slice == 0) {
+    for (int c = threadIdx.x; c < feat_dim; c += blockDim.x)
+      of[(int64_t)j * feat_dim + c] = feat[idx * feat_dim + c];
+    for (int c = threadIdx.x; c < act_dim; c += blockDim.x)
+      oa[(int64_t)j * act_dim + c] = act[idx * act_dim + c];
+  }
+
+  // this block's share of both frames, in image rows; an empty share
+  // still reaches the barrier
+  const int64_t frame_n = (int64_t)rows * W;
+  const int xg = (W + 3) >> 2;
+  const int rchunk = (rows + nslice - 1) / nslice;
+  const int r_lo = slice * rchunk;
+  const int items = max(0, min(rows, r_lo + rchunk) - r_lo) * xg;
+  float* __restrict__ o0 = ofr + (int64_t)j * frame_n;
+  float* __restrict__ o1 = onfr + (int64_t)j * frame_n;
+
+  __syncthreads();
+  const int64_t last = s_last;
+  if (slice == 0) {
+    for (int c = threadIdx.x; c < feat_dim; c += blockDim.x)
+      onf[(int64_t)j * feat_dim + c] = nfeat[last * feat_dim + c];
+  }
+  shift_copy_pair<QUANT, VEC>(frames, nframes, idx * frame_n,
+                              last * frame_n, o0, o1, dy0, dx0, dy1, dx1,
+                              r_lo, items, xg, H, W);
 }
 
 // ---------------------------------------------------------------------------
@@ -1568,22 +1688,21 @@ std::vector<torch::Tensor> per_sample(torch::Tensor tree, int64_t cap,
 // write every field of the transition at ring slot `idx` — replaces the
 // CPU-side encode chain + ~10 aten copies per env step.
 template <bool QUANT>
-__global__ __launch_bounds__(256)
-void visual_store_kernel(const float* __restrict__ feat,
-                         const float* __restrict__ frame,
-                         const float* __restrict__ nfeat,
-                         const float* __restrict__ nframe,
-                         const float* __restrict__ act,
-                         float rew, float done,
-                         float* __restrict__ rfeat,
-                         void* __restrict__ rframe,
-                         float* __restrict__ rnfeat,
-                         void* __restrict__ rnframe,
-                         float* __restrict__ ract,
-                         float* __restrict__ rrew,
-                         float* __restrict__ rdone,
-                         int64_t idx, int feat_dim, int64_t frame_n,
-                         int act_dim) {
+DEVINL void visual_store_slot(const float* __restrict__ feat,
+                              const float* __restrict__ frame,
+                              const float* __restrict__ nfeat,
+                              const float* __restrict__ nframe,
+                              const float* __restrict__ act,
+                              float rew, float done,
+                              float* __restrict__ rfeat,
+                              void* __restrict__ rframe,
+                              float* __restrict__ rnfeat,
+                              void* __restrict__ rnframe,
+                              float* __restrict__ ract,
+                              float* __restrict__ rrew,
+                              float* __restrict__ rdone,
+                              int64_t idx, int feat_dim, int64_t frame_n,
+                              int act_dim) {
   const int slice = blockIdx.x;
   const int nslice = gridDim.x;
   if (slice == 0) {
@@ -1621,6 +1740,60 @@ void visual_store_kernel(const float* __restrict__ feat,
   }
 }
 
+template <bool QUANT>
+__global__ __launch_bounds__(256)
+void visual_store_kernel(const float* __restrict__ feat,
+                         const float* __restrict__ frame,
+                         const float* __restrict__ nfeat,
+                         const float* __restrict__ nframe,
+                         const float* __restrict__ act,
+                         float rew, float done,
+                         float* __restrict__ rfeat,
+                         void* __restrict__ rframe,
+                         float* __restrict__ rnfeat,
+                         void* __restrict__ rnframe,
+                         float* __restrict__ ract,
+                         float* __restrict__ rrew,
+                         float* __restrict__ rdone,
+                         int64_t idx, int feat_dim, int64_t frame_n,
+                         int act_dim) {
+  visual_store_slot<QUANT>(feat, frame, nfeat, nframe, act, rew, done, rfeat,
+                           rframe, rnfeat, rnframe, ract, rrew, rdone, idx,
+                           feat_dim, frame_n, act_dim);
+}
+
+// The store of an n-step ring (set_n_step(n > 1)): the same write plus the
+// episode-boundary flag of the slot and the device mirror of the write
+// head, which the n-step gather reads, so the env step costs no launch
+// more than the 1-step store.
+template <bool QUANT>
+__global__ __launch_bounds__(256)
+void visual_store_n_kernel(const float* __restrict__ feat,
+                           const float* __restrict__ frame,
+                           const float* __restrict__ nfeat,
+                           const float* __restrict__ nframe,
+                           const float* __restrict__ act,
+                           float rew, float done, float end,
+                           float* __restrict__ rfeat,
+                           void* __restrict__ rframe,
+                           float* __restrict__ rnfeat,
+                           void* __restrict__ rnframe,
+                           float* __restrict__ ract,
+                           float* __restrict__ rrew,
+                           float* __restrict__ rdone,
+                           float* __restrict__ rend,
+                           int64_t* __restrict__ ptr_dev,
+                           int64_t idx, int64_t cap, int feat_dim,
+                           int64_t frame_n, int act_dim) {
+  visual_store_slot<QUANT>(feat, frame, nfeat, nframe, act, rew, done, rfeat,
+                           rframe, rnfeat, rnframe, ract, rrew, rdone, idx,
+                           feat_dim, frame_n, act_dim);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    rend[idx] = end;
+    ptr_dev[0] = (idx + 1) % cap;
+  }
+}
+
 void visual_store_into(torch::Tensor feat, torch::Tensor frame,
                        torch::Tensor nfeat, torch::Tensor nframe,
                        torch::Tensor act, double rew, double done,
@@ -1646,6 +1819,64 @@ void visual_store_into(torch::Tensor feat, torch::Tensor frame,
                        ract.data_ptr<float>(), rrew.data_ptr<float>(),
                        rdone.data_ptr<float>(), idx, feat_dim, frame_n,
                        act_dim);
+  };
+  if (quant) L(std::true_type{});
+  else L(std::false_type{});
+}
+
+// visual_store_into for an n-step ring: `end` is the slot's episode_end
+// flag, rend / ptr_dev the ring's episode_end field and write-head mirror.
+void visual_store_into_n(torch::Tensor feat, torch::Tensor frame,
+                         torch::Tensor nfeat, torch::Tensor nframe,
+                         torch::Tensor act, double rew, double done,
+                         double end,
+                         torch::Tensor rfeat, torch::Tensor rframe,
+                         torch::Tensor rnfeat, torch::Tensor rnframe,
+                         torch::Tensor ract, torch::Tensor rrew,
+                         torch::Tensor rdone, torch::Tensor rend,
+                         torch::Tensor ptr_dev, int64_t idx) {
+  CHECK_IN(feat); CHECK_IN(frame); CHECK_IN(nfeat); CHECK_IN(nframe);
+  CHECK_IN(act);
+  CHECK_IN(rfeat); CHECK_IN(rnfeat); CHECK_IN(ract); CHECK_IN(rrew);
+  CHECK_IN(rdone); CHECK_IN(rend);
+  const int64_t cap = rrew.numel();
+  const int feat_dim = (int)feat.numel();
+  const int act_dim = (int)act.numel();
+  const int64_t frame_n = frame.numel();
+  TORCH_CHECK(cap >= 1 && idx >= 0 && idx < cap, "ring slot out of range");
+  TORCH_CHECK(rdone.numel() == cap && rend.numel() == cap &&
+              rfeat.numel() == cap * feat_dim &&
+              rnfeat.numel() == cap * feat_dim &&
+              ract.numel() == cap * act_dim,
+              "ring fields must share one capacity");
+  TORCH_CHECK(nfeat.numel() == feat_dim && nframe.numel() == frame_n,
+              "state and next state differ in shape");
+  TORCH_CHECK(rframe.is_cuda() && rframe.is_contiguous() &&
+              rnframe.is_cuda() && rnframe.is_contiguous() &&
+              rnframe.scalar_type() == rframe.scalar_type() &&
+              rframe.numel() == cap * frame_n &&
+              rnframe.numel() == cap * frame_n, "bad frame storage");
+  const bool quant = rframe.scalar_type() == torch::kUInt8;
+  TORCH_CHECK(quant || rframe.scalar_type() == torch::kFloat32,
+              "frames must be uint8 or float32");
+  TORCH_CHECK(ptr_dev.is_cuda() && ptr_dev.dtype() == torch::kInt64 &&
+              ptr_dev.numel() == 1,
+              "ptr_dev must be an int64 [1] device tensor");
+  const int slices = (int)std::min<int64_t>(8, (frame_n + 4095) / 4096);
+  auto s = cur_stream();
+  auto L = [&](auto q) {
+    hipLaunchKernelGGL((visual_store_n_kernel<decltype(q)::value>),
+                       dim3(std::max(1, slices)), dim3(256), 0, s,
+                       feat.data_ptr<float>(), frame.data_ptr<float>(),
+                       nfeat.data_ptr<float>(), nframe.data_ptr<float>(),
+                       act.data_ptr<float>(), (float)rew, (float)done,
+                       (float)end,
+                       rfeat.data_ptr<float>(), rframe.data_ptr(),
+                       rnfeat.data_ptr<float>(), rnframe.data_ptr(),
+                       ract.data_ptr<float>(), rrew.data_ptr<float>(),
+                       rdone.data_ptr<float>(), rend.data_ptr<float>(),
+                       ptr_dev.data_ptr<int64_t>(), idx, cap, feat_dim,
+                       frame_n, act_dim);
   };
   if (quant) L(std::true_type{});
   else L(std::false_type{});
@@ -1764,6 +1995,105 @@ void visual_sample_into_shift(torch::Tensor feat, torch::Tensor frames,
   else L(std::false_type{}, std::false_type{});
 }
 
+// n-step variant (n > 1) of visual_sample_into (pad == 0, shifts absent)
+// and visual_sample_into_shift (pad >= 1): ep_end is the ring's
+// episode-boundary field and ptr_dev the device mirror of the write head,
+// both read at run time, so a captured launch sees later stores.
+void visual_sample_into_n(torch::Tensor feat, torch::Tensor frames,
+                          torch::Tensor nfeat, torch::Tensor nframes,
+                          torch::Tensor act, torch::Tensor rew,
+                          torch::Tensor done, torch::Tensor ep_end,
+                          torch::Tensor size_dev, torch::Tensor ptr_dev,
+                          torch::Tensor ctr, int64_t seed, int64_t n,
+                          double gamma,
+                          torch::Tensor of, torch::Tensor ofr,
+                          torch::Tensor onf, torch::Tensor onfr,
+                          torch::Tensor oa, torch::Tensor orew,
+                          torch::Tensor od, int64_t pad, int64_t H,
+                          int64_t W, c10::optional<torch::Tensor> shifts) {
+  CHECK_IN(feat); CHECK_IN(nfeat); CHECK_IN(act); CHECK_IN(rew);
+  CHECK_IN(done); CHECK_IN(ep_end);
+  CHECK_IN(of); CHECK_IN(ofr); CHECK_IN(onf); CHECK_IN(onfr); CHECK_IN(oa);
+  CHECK_IN(orew); CHECK_IN(od);
+  TORCH_CHECK(n >= 1 && n <= 64, "n_step must be in 1..64");
+  TORCH_CHECK(pad >= 0 && pad <= 32, "shift pad must be in 0..32");
+  TORCH_CHECK(feat.dim() == 2 && act.dim() == 2 && frames.dim() >= 2,
+              "ring fields must be [capacity, ...]");
+  const int64_t cap = feat.size(0);
+  const int B = (int)of.size(0);
+  const int feat_dim = (int)feat.size(1);
+  const int act_dim = (int)act.size(1);
+  TORCH_CHECK(cap >= 1 && rew.numel() == cap && done.numel() == cap &&
+              ep_end.numel() == cap && nfeat.size(0) == cap &&
+              nfeat.size(1) == feat_dim && act.size(0) == cap &&
+              frames.size(0) == cap,
+              "ring fields must share one capacity");
+  TORCH_CHECK(ptr_dev.is_cuda() && ptr_dev.dtype() == torch::kInt64 &&
+              ptr_dev.numel() == 1 && size_dev.is_cuda() &&
+              size_dev.dtype() == torch::kInt64 && size_dev.numel() == 1 &&
+              ctr.is_cuda() && ctr.dtype() == torch::kInt64 &&
+              ctr.numel() == 1,
+              "size_dev / ptr_dev / ctr must be int64 [1] device tensors");
+  const int64_t frame_n = frames.numel() / cap;
+  TORCH_CHECK(H >= 1 && W >= 1 && frame_n % (H * W) == 0 &&
+              frame_n < ((int64_t)1 << 31),
+              "frame size is not a multiple of H*W");
+  TORCH_CHECK(frames.is_cuda() && frames.is_contiguous() &&
+              nframes.is_cuda() && nframes.is_contiguous() &&
+              nframes.scalar_type() == frames.scalar_type() &&
+              nframes.numel() == frames.numel(), "bad frame storage");
+  TORCH_CHECK(ofr.numel() == (int64_t)B * frame_n &&
+              onfr.numel() == (int64_t)B * frame_n,
+              "batch frames do not match the stored frame size");
+  TORCH_CHECK(of.numel() == (int64_t)B * feat_dim &&
+              onf.numel() == (int64_t)B * feat_dim &&
+              oa.numel() == (int64_t)B * act_dim && orew.numel() == B &&
+              od.numel() == B, "batch fields do not match the batch size");
+  int32_t* oshift = nullptr;
+  if (pad > 0) {
+    TORCH_CHECK(shifts.has_value() && shifts->is_cuda() &&
+                shifts->is_contiguous() &&
+                shifts->scalar_type() == torch::kInt32 &&
+                shifts->numel() == (int64_t)B * 4,
+                "shifts must be an int32 [B,4] device tensor");
+    oshift = shifts->data_ptr<int32_t>();
+  } else {
+    TORCH_CHECK(!shifts.has_value(), "shifts given without a shift pad");
+  }
+  const bool quant = frames.scalar_type() == torch::kUInt8;
+  TORCH_CHECK(quant || frames.scalar_type() == torch::kFloat32,
+              "frames must be uint8 or float32");
+  const int rows = (int)(frame_n / W);
+  // one 16-byte store per 4 pixels needs rows and both bases 16-B aligned
+  const bool vec = W % 4 == 0 &&
+      (reinterpret_cast<uintptr_t>(ofr.data_ptr<float>()) |
+       reinterpret_cast<uintptr_t>(onfr.data_ptr<float>())) % 16 == 0;
+  auto s = cur_stream();
+  hipLaunchKernelGGL(bump_counter_kernel, dim3(1), dim3(1), 0, s,
+                     ctr.data_ptr<int64_t>());
+  const int slices = (int)std::min<int64_t>(8, (frame_n + 4095) / 4096);
+  dim3 grid(B, std::max(1, slices));
+  auto L = [&](auto q, auto v) {
+    hipLaunchKernelGGL(
+        (visual_gather_n_kernel<decltype(q)::value, decltype(v)::value>),
+        grid, dim3(256), 0, s, feat.data_ptr<float>(), frames.data_ptr(),
+        nfeat.data_ptr<float>(), nframes.data_ptr(),
+        act.data_ptr<float>(), rew.data_ptr<float>(),
+        done.data_ptr<float>(), ep_end.data_ptr<float>(),
+        size_dev.data_ptr<int64_t>(), ptr_dev.data_ptr<int64_t>(),
+        ctr.data_ptr<int64_t>(), (uint64_t)seed, of.data_ptr<float>(),
+        ofr.data_ptr<float>(), onf.data_ptr<float>(),
+        onfr.data_ptr<float>(), oa.data_ptr<float>(),
+        orew.data_ptr<float>(), od.data_ptr<float>(), oshift, feat_dim,
+        act_dim, (int)pad, rows, (int)H, (int)W, cap, (int)n,
+        (float)gamma);
+  };
+  if (quant && vec) L(std::true_type{}, std::true_type{});
+  else if (quant) L(std::true_type{}, std::false_type{});
+  else if (vec) L(std::false_type{}, std::true_type{});
+  else L(std::false_type{}, std::false_type{});
+}
+
 void bump_counter(torch::Tensor ctr) {
   hipLaunchKernelGGL(bump_counter_kernel, dim3(1), dim3(1), 0, cur_stream(),
                      ctr.data_ptr<int64_t>());
@@ -1872,7 +2202,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("visual_sample_into", &visual_sample_into);
   m.def("visual_sample_into_shift", &visual_sample_into_shift,
         "visual_sample_into with DrQ random-shift augmentation");
+  m.def("visual_sample_into_n", &visual_sample_into_n,
+        "n-step visual_sample_into, with or without random shift");
   m.def("visual_store_into", &visual_store_into);
+  m.def("visual_store_into_n", &visual_store_into_n,
+        "visual_store_into plus episode_end and the write-head mirror");
   m.def("philox_randn_", &philox_randn_);
   m.def("bump_counter", &bump_counter);
 }
