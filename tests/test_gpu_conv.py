@@ -6,6 +6,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import kernel_refs as kr
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
@@ -390,9 +392,9 @@ def test_visual_act_graph():
 
 def test_visual_trunk_b1_parity(ext):
     """Fused single-workgroup B=1 conv trunk vs the tiled conv kernels
-    and a plain torch reference, both visual geometries."""
+    and a plain torch reference, both visual geometries and grayscale."""
     import torch.nn.functional as TF
-    for (C, H, W) in [(3, 84, 84), (3, 64, 64)]:
+    for (C, H, W) in [(3, 84, 84), (3, 64, 64), (1, 64, 64)]:
         torch.manual_seed(9)
         x = torch.randn(C, H, W, device=DEV)
         w1 = torch.randn(32, C, 8, 8, device=DEV) * 0.1
@@ -429,3 +431,51 @@ def test_visual_actor_b1_fast_path_matches_batched(ext):
                       deterministic=True, with_logprob=False)
     assert torch.allclose(a1.reshape(-1), a2[0], atol=5e-4, rtol=1e-4), \
         (a1.reshape(-1) - a2[0]).abs().max()
+
+
+def _trunk_id(case):
+    return "x".join(str(v) for v in case[0])
+
+
+@pytest.mark.parametrize("case", kr.TRUNK_CASES, ids=_trunk_id)
+def test_visual_trunk_b1_output_larger_than_frame(ext, case):
+    """Strides 4/1/1 (1x36x36: layer 2 writes 1600 floats, the frame has
+    1296): layer 2's output is larger than the frame, so it must not be
+    placed over layer 1's output, which layer 2 is still reading.
+    Integer operands keep all three layers exact (test_kernel_refs.py),
+    so the fused trunk must equal the float64 reference bit for bit."""
+    vis, filters, strides = case
+    x, ws, bs = kr.trunk_operands(vis, filters)
+    ref = kr.trunk_ref(x, ws, bs, strides)[-1][0].reshape(-1)
+    dev = [t.to(DEV) for t in (x, ws[0], bs[0], ws[1], bs[1], ws[2], bs[2])]
+    out = ext.visual_trunk_b1(*dev, *strides)
+    msg = kr.describe_mismatch(out.cpu().double(), ref)
+    assert msg == "", msg
+
+
+@pytest.mark.parametrize("case", kr.TRUNK_CASES, ids=_trunk_id)
+def test_cnn_trunk_b1_env_matches_tiled_path(case, monkeypatch):
+    """_CnnTrunk with TAC_AMD_TRUNK_B1=1 returns the tiled-path answer
+    at the geometries above: with integer conv operands both conv stacks
+    are exact, so the dense layers see identical bits."""
+    from torch_actor_critic_amd.models.visual import simple_cnn
+    vis, filters, strides = case
+    x, ws, bs = kr.trunk_operands(vis, filters)
+    net = simple_cnn(vis, list(filters), [8, 4, 3], list(strides))
+    with torch.no_grad():
+        for i in range(3):
+            conv = getattr(net, f"conv_{i}")
+            conv.weight.copy_(ws[i])
+            conv.bias.copy_(bs[i])
+    net = net.to(DEV)
+    frame = x.unsqueeze(0).to(DEV)
+    with torch.no_grad():
+        monkeypatch.delenv("TAC_AMD_TRUNK_B1", raising=False)
+        tiled = net(frame)
+        flat_ref = net.flatten(net.conv_2(net.conv_1(net.conv_0(frame))))
+        monkeypatch.setenv("TAC_AMD_TRUNK_B1", "1")
+        fused = net(frame)
+    want = kr.trunk_ref(x, ws, bs, strides)[-1][0].reshape(1, -1)
+    assert kr.describe_mismatch(flat_ref.cpu().double(), want) == ""
+    assert tiled.shape == fused.shape == (1, 1)
+    assert torch.equal(fused, tiled), (fused, tiled)

@@ -35,8 +35,7 @@ DEV = "cuda:0"
 @pytest.mark.parametrize("M,N,K", [
     (64, 256, 17), (64, 256, 256), (64, 6, 256), (64, 1, 262),
     (1, 256, 17), (4096, 256, 256), (100, 23, 393), (64, 56, 257),
-    # large-M shapes: exercise the N-tile-reuse (NT) path incl. a
-    # partial last 64-wide sub-tile and an odd N
+    # first-generation kernel only; test_gpu_mgemm.py covers the live mgemm
     (2048, 393, 256), (4096, 128, 300), (1024, 257, 129),
 ])
 def test_linear_fwd_fp32_parity(ext, M, N, K):

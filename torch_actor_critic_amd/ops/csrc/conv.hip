@@ -986,7 +986,8 @@ void visual_trunk_b1_kernel(const float* __restrict__ x,
                             const float* __restrict__ w3,
                             const float* __restrict__ b3,
                             float* __restrict__ out,
-                            ConvDims d1, ConvDims d2, ConvDims d3) {
+                            ConvDims d1, ConvDims d2, ConvDims d3,
+                            int a2_off) {
   __shared__ __attribute__((aligned(16))) float lds[40960];  // 160 KB
   const int tid = threadIdx.x;
   const int nthr = blockDim.x;
@@ -995,8 +996,10 @@ void visual_trunk_b1_kernel(const float* __restrict__ x,
   const int in_n = d1.IC * d1.IH * d1.IW;
   float* a1 = lds + in_n;                            // 32*OH1*OW1
   const int a1_n = d1.OC * d1.OH * d1.OW;
-  float* a2 = lds;                                   // reuses input slab
-  const int a2_n = d2.OC * d2.OH * d2.OW;
+  // layer 2 writes a2 while it still reads a1, so the two must not
+  // overlap: a2 reuses the input slab when it fits there (a2_off = 0),
+  // else the host places it behind a1
+  float* a2 = lds + a2_off;
 
   const int lane = tid & 63;
   const int wid = tid >> 6;
@@ -1325,7 +1328,9 @@ torch::Tensor visual_trunk_b1(torch::Tensor x, torch::Tensor w1,
   const int in_n = d1.IC * d1.IH * d1.IW;
   const int a1_n = d1.OC * d1.OH * d1.OW;
   const int a2_n = d2.OC * d2.OH * d2.OW;
-  TORCH_CHECK(in_n + a1_n <= 40960 && a2_n <= 40960,
+  // a1 lives at [in_n, in_n + a1_n); a2 must stay clear of it
+  const int a2_off = a2_n <= in_n ? 0 : in_n + a1_n;
+  TORCH_CHECK(in_n + a1_n <= 40960 && a2_off + a2_n <= 40960,
               "visual_trunk_b1: activations exceed the 160 KB LDS plan");
   TORCH_CHECK(d1.KH == 8 && d2.KH == 4 && d3.KH == 3 &&
               d1.KW == 8 && d2.KW == 4 && d3.KW == 3,
@@ -1338,7 +1343,7 @@ torch::Tensor visual_trunk_b1(torch::Tensor x, torch::Tensor w1,
                      stream(), x.data_ptr<float>(), w1.data_ptr<float>(),
                      bp(b1), w2.data_ptr<float>(), bp(b2),
                      w3.data_ptr<float>(), bp(b3), out.data_ptr<float>(),
-                     d1, d2, d3);
+                     d1, d2, d3, a2_off);
   return out;
 }
 
