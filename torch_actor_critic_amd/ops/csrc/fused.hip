@@ -589,6 +589,254 @@ void mgemm_combine_kernel(MGemm g, int split, bool relu) {
 }
 
 // ---------------------------------------------------------------------------
+// Small-shape mgemm (bf16 compute, M <= 128, K <= 256, K2 <= 256): the
+// batch-64 update's GEMMs are latency-bound, not throughput-bound.  The
+// pipelined kernel above walks K in 128-wide steps with a dependent
+// global round trip per step and a third one for the bias; here every
+// global load of the block (A, mask, W, the SUM2 pair, bias) is issued
+// before the first wait, the whole K extent is converted into LDS behind
+// ONE barrier, and the MFMA chain runs over it.  Tiles are TM x TN
+// (template) so a 64-row problem spreads over more CUs.
+//
+// Same bits as mgemm_kernel<true, ...>: identical LDS content layout
+// (element k of a row at column k), identical lane -> fragment map,
+// K-chunks of 32 ascending from a zero accumulator, operand 1 then the
+// SUM2 operand, one fp32 -> bf16 rounding per operand, fp32 bias add and
+// ReLU after the chain.  K is zero-padded to 32 (the kernel above pads to
+// 128; its extra all-zero chunks add exact zeros).
+// ---------------------------------------------------------------------------
+
+constexpr int SKMAX = 256;   // host gate: K <= SKMAX and K2 <= SKMAX
+constexpr int SLPAD = 8;     // row stride = Kp + 8 halves: (16k + 4) dwords,
+                             // 16 consecutive rows land in distinct banks
+
+// 4-lanes-per-row float4 form: aligned rows wholly inside the operand.
+DEVINL bool small_vec_ok(const float* src, const float* mask, int r0, int R,
+                         int bound, int K, int ld) {
+  return (r0 + R <= bound) && ((ld & 3) == 0) && ((K & 3) == 0)
+         && ((((uintptr_t)src | (uintptr_t)mask) & 15) == 0);
+}
+
+// Issue all global loads of an R x K tile (rows r0.., bound `bound`) into
+// registers; nothing here waits on a load.  Out-of-range lanes read a
+// clamped (valid) address and are zeroed by small_write.
+//  * vec:   4 lanes x float4 per row; R = 32 splits K over two row sets
+//  * !vec:  16 lanes x dword per row, rows rr + 16p
+template <int R, bool MASK, bool R1>
+DEVINL void small_load(float (&v)[R], float (&mk)[MASK ? R : 1],
+                       float (&ra)[R / 16], bool vec,
+                       const float* src, const float* mask,
+                       int r0, int bound, int K, int ld,
+                       const float* r1c, const float* r1r) {
+  const int tid = threadIdx.x;
+  if (vec) {
+    constexpr int G = 64 / R;
+    constexpr int NQ = SKMAX / 16 / G;
+    const int gr = r0 + ((tid >> 2) & (R - 1));
+    const int kg = (tid >> 2) / R;
+    const int c = tid & 3;
+    if constexpr (R1) ra[0] = r1c[gr];
+    const float* base = R1 ? r1r : src + (int64_t)gr * ld;
+    const float* mbase = MASK ? mask + (int64_t)gr * ld : nullptr;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      if (q * G * 16 < K) {
+        const int col = min(((q * G + kg) * 4 + c) * 4, K - 4);
+        float4 f = *(const float4*)(base + col);
+        v[q*4+0] = f.x; v[q*4+1] = f.y; v[q*4+2] = f.z; v[q*4+3] = f.w;
+        if constexpr (MASK) {
+          float4 h = *(const float4*)(mbase + col);
+          mk[q*4+0] = h.x; mk[q*4+1] = h.y; mk[q*4+2] = h.z; mk[q*4+3] = h.w;
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          v[q*4+j] = 0.f;
+          if constexpr (MASK) mk[q*4+j] = 0.f;
+        }
+      }
+    }
+  } else {
+    const int rr = tid >> 4;
+    const int cc = tid & 15;
+#pragma unroll
+    for (int p = 0; p < R / 16; ++p) {
+      const bool rows_in = r0 + 16 * p < bound;
+      const int gr = min(r0 + rr + 16 * p, bound - 1);
+      if constexpr (R1) ra[p] = r1c[gr];
+#pragma unroll
+      for (int q = 0; q < SKMAX / 16; ++q) {
+        if (rows_in && q * 16 < K) {
+          const int col = min(cc + 16 * q, K - 1);
+          if constexpr (R1) v[p*16+q] = r1r[col];
+          else v[p*16+q] = src[(int64_t)gr * ld + col];
+          if constexpr (MASK) mk[p*16+q] = mask[(int64_t)gr * ld + col];
+        } else {
+          v[p*16+q] = 0.f;
+          if constexpr (MASK) mk[p*16+q] = 0.f;
+        }
+      }
+    }
+  }
+}
+
+// Convert a loaded tile and write it to LDS at columns [0, Kp) of `d`
+// (row stride S halves), zero beyond the operand's bounds.  Same vec /
+// r0 / bound / K as the matching small_load.
+template <int R, bool MASK, bool R1>
+DEVINL void small_write(__bf16* d, int S, const float (&v)[R],
+                        const float (&mk)[MASK ? R : 1],
+                        const float (&ra)[R / 16], bool vec,
+                        int r0, int bound, int K, int Kp) {
+  const int tid = threadIdx.x;
+  if (vec) {
+    constexpr int G = 64 / R;
+    constexpr int NQ = SKMAX / 16 / G;
+    const int row = (tid >> 2) & (R - 1);
+    const int kg = (tid >> 2) / R;
+    const int c = tid & 3;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      if (q * G * 16 < Kp) {
+        const int col = ((q * G + kg) * 4 + c) * 4;
+        const bool in = col < K;
+        union { __bf16 h[4]; uint2 u; } pk;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          float x = v[q*4+j];
+          if constexpr (R1) x = ra[0] * x;
+          if constexpr (MASK) x = mk[q*4+j] > 0.f ? x : 0.f;
+          pk.h[j] = (__bf16)(in ? x : 0.f);
+        }
+        *(uint2*)&d[row * S + col] = pk.u;
+      }
+    }
+  } else {
+    const int rr = tid >> 4;
+    const int cc = tid & 15;
+#pragma unroll
+    for (int p = 0; p < R / 16; ++p) {
+      const int row = rr + 16 * p;
+      const bool row_in = r0 + row < bound;
+#pragma unroll
+      for (int q = 0; q < SKMAX / 16; ++q) {
+        if (q * 16 < Kp) {
+          const int col = cc + 16 * q;
+          float x = v[p*16+q];
+          if constexpr (R1) x = ra[p] * x;
+          if constexpr (MASK) x = mk[p*16+q] > 0.f ? x : 0.f;
+          d[row * S + col] = (__bf16)((row_in && col < K) ? x : 0.f);
+        }
+      }
+    }
+  }
+}
+
+template <int TM, int TN, bool MASK, bool RELU, bool SUM2, bool R1>
+__global__ __launch_bounds__(256)
+void mgemm_small_kernel(MGemm g) {
+  static_assert((TM == 32 || TM == 64) && (TN == 32 || TN == 64), "tile");
+  static_assert(!(SUM2 && R1), "R1 has no second operand");
+  constexpr int WM = TM / 2, WN = TN / 2;      // per-wave sub-tile
+  constexpr int MI = WM / 16, NI = WN / 16;
+  constexpr int KT = SUM2 ? 2 * SKMAX : SKMAX;
+  __shared__ __attribute__((aligned(16))) __bf16 smem[(TM + TN)
+                                                      * (KT + SLPAD)];
+  const MProb& p = g.p[blockIdx.z];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = tid >> 6;
+  const int wrow = (wid >> 1) * WM;
+  const int wcol = (wid & 1) * WN;
+  const int bm0 = blockIdx.x * TM;
+  const int bn0 = blockIdx.y * TN;
+  const int crow = (lane >> 4) * 4, ccol = lane & 15;
+
+  const int Kp1 = (g.K + 31) & ~31;
+  const int Kp2 = SUM2 ? ((g.K2 + 31) & ~31) : 0;
+  const int S = Kp1 + Kp2 + SLPAD;
+  __bf16* xs = smem;
+  __bf16* ws = smem + TM * S;
+
+  // every global load of the block, issued back to back
+  float bv[NI];
+#pragma unroll
+  for (int ni = 0; ni < NI; ++ni) {
+    const int gcol = bn0 + wcol + ni * 16 + ccol;
+    bv[ni] = (p.bias && gcol < g.N) ? p.bias[gcol] : 0.f;
+  }
+  float va[TM], ma[MASK ? TM : 1], ra[TM / 16], vb[TN], nomask[1],
+        rb[TN / 16];
+  const float* a_src = R1 ? p.r1_row : p.x;
+  const bool veca = small_vec_ok(a_src, MASK ? p.mask : nullptr, bm0, TM,
+                                 g.M, g.K, g.lda);
+  const bool vecb = small_vec_ok(p.w, nullptr, bn0, TN, g.N, g.K, g.K);
+  small_load<TM, MASK, R1>(va, ma, ra, veca, p.x, p.mask, bm0, g.M, g.K,
+                           g.lda, p.r1_col, p.r1_row);
+  small_load<TN, false, false>(vb, nomask, rb, vecb, p.w, nullptr, bn0, g.N,
+                               g.K, g.K, nullptr, nullptr);
+  float va2[SUM2 ? TM : 1], ma2[(SUM2 && MASK) ? TM : 1], vb2[SUM2 ? TN : 1];
+  bool veca2 = false, vecb2 = false;
+  if constexpr (SUM2) {
+    veca2 = small_vec_ok(p.x2, MASK ? p.mask2 : nullptr, bm0, TM, g.M, g.K2,
+                         g.K2);
+    vecb2 = small_vec_ok(p.w2, nullptr, bn0, TN, g.N, g.K2, g.K2);
+    small_load<TM, MASK, false>(va2, ma2, ra, veca2, p.x2, p.mask2, bm0, g.M,
+                                g.K2, g.K2, nullptr, nullptr);
+    small_load<TN, false, false>(vb2, nomask, rb, vecb2, p.w2, nullptr, bn0,
+                                 g.N, g.K2, g.K2, nullptr, nullptr);
+  }
+
+  small_write<TM, MASK, R1>(xs, S, va, ma, ra, veca, bm0, g.M, g.K, Kp1);
+  small_write<TN, false, false>(ws, S, vb, nomask, rb, vecb, bn0, g.N, g.K,
+                                Kp1);
+  if constexpr (SUM2) {
+    small_write<TM, MASK, false>(xs + Kp1, S, va2, ma2, ra, veca2, bm0, g.M,
+                                 g.K2, Kp2);
+    small_write<TN, false, false>(ws + Kp1, S, vb2, nomask, rb, vecb2, bn0,
+                                  g.N, g.K2, Kp2);
+  }
+  __syncthreads();
+
+  f32x4 acc[MI][NI] = {};
+  const int arow = lane & 15;
+  const int ak0 = (lane >> 4) * 8;
+  const __bf16* xr = xs + (wrow + arow) * S + ak0;
+  const __bf16* wr = ws + (wcol + arow) * S + ak0;
+  const int Kt = Kp1 + Kp2;
+  for (int kk = 0; kk < Kt; kk += 32) {
+    bf16x8 b[NI];
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni)
+      b[ni] = *(const bf16x8*)&wr[ni * 16 * S + kk];
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi) {
+      bf16x8 a = *(const bf16x8*)&xr[mi * 16 * S + kk];
+#pragma unroll
+      for (int ni = 0; ni < NI; ++ni)
+        acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            a, b[ni], acc[mi][ni], 0, 0, 0);
+    }
+  }
+
+#pragma unroll
+  for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int grow = bm0 + wrow + mi * 16 + crow + r;
+        const int gcol = bn0 + wcol + ni * 16 + ccol;
+        if (grow < g.M && gcol < g.N) {
+          float v = acc[mi][ni][r];
+          if (p.bias) v += bv[ni];
+          if constexpr (RELU) v = fmaxf(v, 0.f);
+          p.y[(int64_t)grow * g.ldy + gcol] = v;
+        }
+      }
+}
+
+// ---------------------------------------------------------------------------
 // The per-element Adam update, shared by adam_t_kernel and the wgrad
 // epilogues that apply Adam to the gradient they just finished
 // (mwgrad_het_adam): m, v, p and the optional polyak target at flat
@@ -2256,6 +2504,46 @@ inline const float* fptr(const c10::optional<torch::Tensor>& t) {
   return t.has_value() ? t->data_ptr<float>() : nullptr;
 }
 
+// TAC_AMD_MGEMM_SMALL: 1 (default) routes bf16 launches with M <= 128,
+// K <= 256 (K2 <= 256) to mgemm_small_kernel, 0 keeps the pipelined
+// kernel for everything.  A plain global so mgemm_small_mode() can flip it
+// inside one process.
+static int g_small_mode = -1;
+
+static int small_mode() {
+  if (g_small_mode < 0) {
+    const char* e = getenv("TAC_AMD_MGEMM_SMALL");
+    g_small_mode = e ? (atoi(e) != 0) : 1;
+  }
+  return g_small_mode;
+}
+
+int64_t mgemm_small_mode(int64_t mode) {
+  const int prev = small_mode();
+  TORCH_CHECK(mode == 0 || mode == 1, "mgemm_small_mode: 0 or 1");
+  g_small_mode = (int)mode;
+  return prev;
+}
+
+inline bool small_gate(bool bf16, int split, int nt, int64_t M, int64_t K,
+                       bool sum2, int64_t K2) {
+  return small_mode() != 0 && bf16 && split == 1 && nt == 1 && M <= 128
+         && K <= SKMAX && (!sum2 || K2 <= SKMAX);
+}
+
+// One tile shape is built: 32x32.  At M = 64 it spreads a 256-wide layer
+// over 16 blocks per problem with 32 + 32 + 32 staged values per thread.
+// 64x64 and 32x64 with the same whole-K staging were measured slower on
+// every flagship launch (OPTIMIZATION_LOG.md, "Small-shape mgemm").
+template <bool MASK, bool RELU, bool SUM2, bool R1>
+static void launch_small(const MGemm& g) {
+  constexpr int T = 32;
+  dim3 grid((unsigned)((g.M + T - 1) / T), (unsigned)((g.N + T - 1) / T),
+            (unsigned)g.nz);
+  hipLaunchKernelGGL((mgemm_small_kernel<T, T, MASK, RELU, SUM2, R1>), grid,
+                     dim3(256), 0, stream(), g);
+}
+
 void mgemm(std::vector<torch::Tensor> xs, std::vector<torch::Tensor> ws,
            std::vector<c10::optional<torch::Tensor>> bs,
            std::vector<torch::Tensor> ys,
@@ -2325,6 +2613,15 @@ void mgemm(std::vector<torch::Tensor> xs, std::vector<torch::Tensor> ws,
   if (nt_env == 0) nt = 1;
   else if (nt_env > 1 && split == 1 && gy >= 2)
     nt = std::min(nt_env, gy);
+  if (small_gate(bf16, split, nt, M, K, sum2, K2)) {
+    #define S2(m, r) do { \
+        if (sum2) launch_small<m, r, true, false>(g); \
+        else launch_small<m, r, false, false>(g); } while (0)
+    if (has_mask) { if (relu) S2(true, true); else S2(true, false); }
+    else          { if (relu) S2(false, true); else S2(false, false); }
+    #undef S2
+    return;
+  }
   const int gy_nt = (gy + nt - 1) / nt;
   dim3 grid(gx, nt > 1 ? gy_nt : gy, nz * split);
   auto L = [&](auto b, auto m, auto r, auto s) {
@@ -2401,6 +2698,10 @@ void mgemm_r1(std::vector<torch::Tensor> cols,
     g.p[z].w = ws[z].data_ptr<float>();
     g.p[z].y = ys[z].data_ptr<float>();
     g.p[z].mask = masks[z].data_ptr<float>();
+  }
+  if (small_gate(*g_bf16_flag, 1, 1, M, K, false, 0)) {
+    launch_small<true, false, false, true>(g);
+    return;
   }
   dim3 grid((unsigned)((M + TB - 1) / TB), (unsigned)((N + TB - 1) / TB),
             nz);
@@ -3271,6 +3572,9 @@ void register_fused(pybind11::module_& m) {
         "multi-problem MFMA GEMM (fwd-form, strided, masked, sum2)");
   m.def("mgemm_r1", &fused::mgemm_r1,
         "masked GEMM whose A operand is a rank-1 product formed on read");
+  m.def("mgemm_small_mode", &fused::mgemm_small_mode,
+        "set TAC_AMD_MGEMM_SMALL's mode (0 = pipelined kernel only), "
+        "returns the previous mode");
   m.def("mwgrad", &fused::mwgrad, "multi-problem wgrad + fused db");
   m.def("mwgrad_het", &fused::mwgrad_het,
         "heterogeneous multi-problem wgrad: one launch per phase");
