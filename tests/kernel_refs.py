@@ -1,6 +1,7 @@
 """Float64 CPU references, operand generators and case tables shared by
-test_gpu_mgemm.py, test_gpu_conv_exact.py, conv_lds_worker.py and the
-CPU precondition test (test_kernel_refs.py).  Plain helper module, not a
+test_gpu_mgemm.py, test_gpu_conv_exact.py, conv_lds_worker.py,
+test_gpu_wgrad.py, wgrad_env_worker.py, test_gpu_adam_t.py and the CPU
+precondition test (test_kernel_refs.py).  Plain helper module, not a
 conftest.
 
 Two operand kinds:
@@ -422,3 +423,358 @@ def uncovered(geom):
         for ox in range(OW):
             cov[oy * S:oy * S + KH, ox * S:ox * S + KW] = True
     return ~cov
+
+
+# ---------------------------------------------------------------------------
+# dense wgrad (fused.hip: mwgrad, mwgrad_het, mwgrad_het_adam)
+# ---------------------------------------------------------------------------
+
+@dataclass(frozen=True)
+class WgProb:
+    """One wgrad problem: dW[N, K] = dYeff^T X, db[N] = column sums."""
+    M: int
+    N: int
+    K: int
+    lddy: Optional[int] = None           # None: N (contiguous dy and mask)
+    ldx: Optional[int] = None            # None: K
+    x_off: int = 0
+    mask: bool = False
+    bias: bool = True
+
+    @property
+    def ld_dy(self):
+        return self.lddy or self.N
+
+    @property
+    def ld_x(self):
+        return self.ldx or self.K
+
+
+@dataclass(frozen=True)
+class WgCase:
+    """One mwgrad launch: nz <= 2 problems of one shape and layout."""
+    name: str
+    M: int
+    N: int
+    K: int
+    nz: int = 1
+    lddy: Optional[int] = None
+    ldx: Optional[int] = None
+    x_off: int = 0
+    mask: bool = False
+    bias: Tuple[bool, ...] = (True,)     # per problem
+    # expected host plan per dtype: (split, rows of the last slab), the
+    # string "split" (any split > 1) or None (not pinned)
+    expect: Tuple = (None, None)         # (fp32, bf16)
+
+    @property
+    def problems(self):
+        return [WgProb(self.M, self.N, self.K, self.lddy, self.ldx,
+                       self.x_off, self.mask, self.bias[z])
+                for z in range(self.nz)]
+
+
+MWGRAD_CASES = [
+    # all edges, one K-step
+    WgCase("tile_tails", 5, 3, 7, expect=((1, 5), (1, 5))),
+    # single row, two n-tiles
+    WgCase("m1", 1, 70, 17, expect=((1, 1), (1, 1))),
+    # one-row last slab
+    WgCase("m17", 17, 70, 33, expect=((2, 1), (1, 17))),
+    # width-1 critic output layer
+    WgCase("n1", 64, 1, 262, expect=((4, 16), (1, 64))),
+    # ragged last slab, mask, twin critics
+    WgCase("ragged_masked_nz2", 70, 33, 130, nz=2, mask=True,
+           bias=(True, True), expect=((5, 6), (2, 6))),
+    # lddy % 4 == 0, ldx % 4 == 0 and a 16-byte-aligned offset: the bf16
+    # float4 interior path for dy, mask and x
+    WgCase("interior_strided", 130, 70, 130, nz=2, lddy=72, ldx=136,
+           x_off=4, mask=True, bias=(True, True),
+           expect=((9, 2), (3, 2))),
+    # the scalar path with an odd offset
+    WgCase("edge_strided", 70, 40, 33, lddy=48, ldx=80, x_off=11,
+           mask=True, expect=("split", "split")),
+    # db optional per problem
+    WgCase("nobias_mixed", 70, 33, 40, nz=2, bias=(True, False)),
+    # 384 tiles: un-split loop over several K-steps with a ragged tail
+    # (fp32: 9 K-steps of 16 rows, bf16: 3 of 64; 130 = 2 * 64 + 2)
+    WgCase("unsplit_multi_step", 130, 512, 1536, nz=2, bias=(True, True),
+           expect=((1, 130), (1, 130))),
+]
+
+MWGRAD_ROUNDING_CASES = ["ragged_masked_nz2", "interior_strided"]
+
+
+def mwgrad_case(name):
+    return next(c for c in MWGRAD_CASES if c.name == name)
+
+
+@dataclass(frozen=True)
+class HetCase:
+    name: str
+    problems: Tuple[WgProb, ...]
+
+
+MWGRAD_HET_CASES = [
+    # the batch-64 phase table: fp32 split 4, bf16 un-split single K-step
+    HetCase("phase64", (WgProb(64, 70, 23, ldx=32, x_off=5),
+                        WgProb(64, 6, 64, mask=True),
+                        WgProb(64, 1, 70))),
+    # per-problem M: fp32 split 5, bf16 split 2; the M = 5 problem must
+    # get exact zeros from every later slab
+    HetCase("mixed_m", (WgProb(70, 70, 130, mask=True),
+                        WgProb(5, 33, 40, lddy=36, ldx=48, x_off=3),
+                        WgProb(64, 1, 70, bias=False))),
+    HetCase("single", (WgProb(5, 3, 7),)),
+    # odd tile counts on both axes: padded 2x2 cluster slots; 31 linear
+    # and 33 clustered blocks, so the padded grid (40) overshoots
+    HetCase("xcd_pad", (WgProb(70, 130, 70, mask=True),
+                        WgProb(70, 3, 7),
+                        WgProb(70, 200, 330, ldx=336, x_off=4))),
+    # M >= 1024 with every (rn, rk) combination under RNRK, ragged 6-row
+    # last slab
+    HetCase("big", (WgProb(1030, 130, 200, mask=True),
+                    WgProb(1030, 70, 130),
+                    WgProb(1030, 1, 140),
+                    WgProb(1030, 130, 40, lddy=132, mask=True))),
+    # 384 tiles: un-split, several K-steps, 12 problems (the MAXW limit)
+    HetCase("many_tiles", (WgProb(130, 250, 500, mask=True),)
+            + tuple(WgProb(130, 256, 512, mask=(i % 2 == 1))
+                    for i in range(11))),
+]
+
+MWGRAD_HET_ROUNDING_CASES = ["phase64", "mixed_m"]
+
+# (split, m_chunk, chunks, blk) keyed by (case, bf16, xcd, rnrk) where the
+# plan is pinned; asserted on the CPU (test_kernel_refs.py)
+HET_PLANS = {
+    ("phase64", False, False, False): (4, 16, 4, 5),
+    ("phase64", True, False, False): (1, 64, 1, 5),
+    ("mixed_m", False, False, False): (5, 16, 5, 9),
+    ("mixed_m", True, False, False): (2, 64, 2, 9),
+    ("single", False, False, False): (1, 16, 1, 1),
+    ("single", True, False, False): (1, 64, 1, 1),
+    ("xcd_pad", False, False, False): (5, 16, 5, 31),
+    ("xcd_pad", True, False, False): (2, 64, 2, 31),
+    ("xcd_pad", False, True, False): (5, 16, 5, 33),
+    ("xcd_pad", True, True, False): (2, 64, 2, 33),
+    ("big", False, False, False): (13, 80, 65, 24),
+    ("big", True, False, False): (9, 128, 17, 24),
+    ("big", True, False, True): (17, 64, 17, 12),
+    ("many_tiles", False, False, False): (1, 144, 9, 384),
+    ("many_tiles", True, False, False): (1, 192, 3, 384),
+}
+
+
+def het_case(name):
+    return next(c for c in MWGRAD_HET_CASES if c.name == name)
+
+
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def mwgrad_plan(M, N, K, nz, bf16):
+    """The host launch plan of fused.hip::mwgrad:
+    (split, m_chunk, chunks, tiles)."""
+    bk = 64 if bf16 else 16
+    chunks = _cdiv(M, bk)
+    tiles = _cdiv(N, 64) * _cdiv(K, 64) * nz
+    split = max(1, min(chunks, (384 + tiles - 1) // tiles))
+    m_chunk = _cdiv(_cdiv(M, split), bk) * bk
+    split = _cdiv(M, m_chunk)
+    return split, m_chunk, chunks, tiles
+
+
+def het_tiles(problems, bf16, xcd=False, rnrk=False):
+    """Per problem (rn, rk, bx, bk_t, slots) as mwgrad_het_impl lays the
+    block table out; slots counts the padded 2x2 cluster slots under xcd."""
+    out = []
+    for p in problems:
+        big = rnrk and bf16 and p.M >= 1024
+        rn = 2 if big and p.N >= 128 else 1
+        rk = 2 if big and p.K >= 128 else 1
+        bx = _cdiv(p.N, 64 * rn)
+        bk_t = _cdiv(p.K, 64 * rk)
+        if xcd:
+            cn, ck = min(2, bx), min(2, bk_t)
+            slots = _cdiv(bx, cn) * _cdiv(bk_t, ck) * cn * ck
+        else:
+            slots = bx * bk_t
+        out.append((rn, rk, bx, bk_t, slots))
+    return out
+
+
+def het_plan(problems, bf16, xcd=False, rnrk=False):
+    """The host launch plan of fused.hip::mwgrad_het_impl / het_split:
+    (split, m_chunk, chunks, blk).  rnrk only applies to mwgrad_het (the
+    Adam-carrying launch and mwgrad_het_adam_split ignore it)."""
+    bk = 64 if bf16 else 16
+    blk = sum(t[4] for t in het_tiles(problems, bf16, xcd, rnrk))
+    max_m = max(p.M for p in problems)
+    chunks = _cdiv(max_m, bk)
+    split = max(1, min(chunks, (384 + blk - 1) // blk, 64))
+    m_chunk = _cdiv(_cdiv(max_m, split), bk) * bk
+    split = _cdiv(max_m, m_chunk)
+    return split, m_chunk, chunks, blk
+
+
+@dataclass
+class WgOps:
+    """CPU operands of one wgrad problem.  dy / mask / x are the full
+    storage tensors ([M, lddy], [M, lddy], [M, ldx]); dy_v / mask_v / x_v
+    the logical [M, N], [M, N], [M, K] blocks."""
+    prob: WgProb
+    dy: torch.Tensor
+    mask: Optional[torch.Tensor]
+    x: torch.Tensor
+
+    @property
+    def dy_v(self):
+        return self.dy[:, :self.prob.N]
+
+    @property
+    def mask_v(self):
+        return None if self.mask is None else self.mask[:, :self.prob.N]
+
+    @property
+    def x_v(self):
+        p = self.prob
+        return self.x[:, p.x_off:p.x_off + p.K]
+
+
+def wgrad_operands(problems, kind, seed=0):
+    """One WgOps per problem.  The pad columns of a strided operand hold
+    ordinary operand values, so a read outside the logical block shows."""
+    g = _gen(5000 + seed)
+    out = []
+    for p in problems:
+        out.append(WgOps(p,
+                         operand(g, (p.M, p.ld_dy), kind),
+                         mask_operand(g, (p.M, p.ld_dy)) if p.mask
+                         else None,
+                         operand(g, (p.M, p.ld_x), kind)))
+    return out
+
+
+def wgrad_ref(dy, x, mask, bf16=False):
+    """(dw64 [N, K], db64 [N], S_dw, S_db) of one wgrad problem from the
+    logical dy [M, N], x [M, K] and mask [M, N] (or None):
+    dyeff = rnd(dy) * (mask > 0), dw = dyeff^T @ rnd(x), db = dyeff.sum(0)
+    in float64; S_* are the same contractions over absolute values.
+    In bf16 mode db sums the bf16-ROUNDED dy: the kernel reads the column
+    sums back from the staged (rounded, masked) LDS tile, not from global
+    memory."""
+    rnd = bf16_round if bf16 else (lambda t: t)
+    dyeff = rnd(dy).double()
+    if mask is not None:
+        dyeff = dyeff * (mask > 0)
+    xr = rnd(x).double()
+    return (dyeff.t() @ xr, dyeff.sum(0),
+            dyeff.abs().t() @ xr.abs(), dyeff.abs().sum(0))
+
+
+def wgrad_refs(ops, bf16=False):
+    return [wgrad_ref(o.dy_v, o.x_v, o.mask_v, bf16) for o in ops]
+
+
+# ---------------------------------------------------------------------------
+# Adam (+ polyak target) as adam_math / polyak_math compute it
+# ---------------------------------------------------------------------------
+
+ADAM_HYPER = dict(lr=2.0 ** -10, b1=0.9, b2=0.999, eps=1e-8, wd=0.0,
+                  rho=0.995)
+
+
+def f32_as_double(v):
+    """A Python float as the kernel receives it: rounded to fp32, widened."""
+    return float(torch.tensor(v, dtype=torch.float32).double())
+
+
+def adam_ref(p, g, m, v, targ, t, hyper):
+    """Float64 Adam step t on fp32 inputs.  Every hyperparameter is taken
+    as the kernel receives it (rounded to fp32, then widened): 0.999f
+    differs from 0.999 by 1.3e-5 relative in 1 - b2, which a reference
+    built from Python doubles would show as an error of the kernel.
+    Returns (p, m, v, targ, u): the new state and the update term u
+    (p_new = p - u); targ is None when no target is given."""
+    h = {k: f32_as_double(x) for k, x in hyper.items()}
+    p, g, m, v = p.double(), g.double(), m.double(), v.double()
+    gi = h["wd"] * p + g
+    mn = h["b1"] * m + (1.0 - h["b1"]) * gi
+    vn = h["b2"] * v + (1.0 - h["b2"]) * gi * gi
+    bc1 = 1.0 - h["b1"] ** float(t)
+    bc2 = 1.0 - h["b2"] ** float(t)
+    u = h["lr"] / bc1 * mn / ((vn / bc2).sqrt() + h["eps"])
+    pn = p - u
+    tn = None
+    if targ is not None:
+        tn = h["rho"] * targ.double() + (1.0 - h["rho"]) * pn
+    return pn, mn, vn, tn, u
+
+
+def ulp32(t64):
+    """Spacing of fp32 at |t| (float64 tensor in, float64 out)."""
+    a = t64.float().abs()
+    return (torch.nextafter(a, torch.full_like(a, float("inf")))
+            - a).double()
+
+
+def adam_bounds(p, g, m, ref, hyper):
+    """Elementwise bounds on |out - adam_ref| for (p, m, v, targ) from the
+    fp32 inputs p, g, m and ref = adam_ref(...):
+      m: three rounded operations on the terms of the sum,
+      v: three rounded operations, relative to v itself,
+      p: one final rounding plus the update's relative error (dominated
+         by the cancellation in 1 - powf(b2, t) at small t),
+      targ: two roundings plus the same update error."""
+    h = {k: f32_as_double(x) for k, x in hyper.items()}
+    pn, mn, vn, tn, u = ref
+    e = 2.0 ** -24
+    bm = 4 * e * (h["b1"] * m.double().abs() + (1.0 - h["b1"])
+                  * (h["wd"] * p.double().abs() + g.double().abs()))
+    bv = 8 * e * vn
+    bp = ulp32(pn) + 1e-4 * u.abs()
+    bt = None if tn is None else 2 * ulp32(tn) + 1e-4 * u.abs()
+    return bp, bm, bv, bt
+
+
+def adam_state(n, step, with_targ, seed=0, g=None):
+    """fp32 (p, g, m, v, targ) for an Adam test: |p|, |targ| <= 1/16 so the
+    final subtraction's ulp does not hide the update, |g| log-uniform in
+    [1e-6, 10] unless given, m = v = 0 at step 1 and non-zero after.
+
+    After step 1 the state keeps |m| >= |g| / 4 and v >= g^2 / 4, as a
+    running average of gradients of this size has.  That is also the
+    range in which a plain fp32 evaluation provably stays within HALF of
+    adam_bounds (the fairness condition test_kernel_refs.py asserts): the
+    error of m is at most 2^-24 * (|m'| + 2 (1 - b1)|gi|), one rounding
+    of the result, one of the product and one of gi, which is below
+    2 * 2^-24 * (b1|m| + (1 - b1)|gi|) once b1|m| >= (1 - b1)|gi|, i.e.
+    |m| >= |gi| / 9.  With |m| << |g| the three roundings can reach 3 of
+    the bound's 4 units (2.05 was measured on 20000 elements), still
+    inside the bound but not inside its half."""
+    gen = _gen(6000 + seed)
+    p = (torch.rand(n, generator=gen) * 2 - 1) / 16
+    targ = (torch.rand(n, generator=gen) * 2 - 1) / 16 if with_targ else None
+    if g is None:
+        mag = 10.0 ** (torch.rand(n, generator=gen) * 7 - 6)
+        sign = torch.randint(0, 2, (n,), generator=gen).float() * 2 - 1
+        g = (mag * sign).float()
+    if step > 1:
+        scale = g.abs().clamp_min(1e-3)
+        msign = torch.randint(0, 2, (n,), generator=gen).float() * 2 - 1
+        m = scale * msign * (torch.rand(n, generator=gen) + 0.25)
+        v = scale * scale * (torch.rand(n, generator=gen) + 0.25)
+    else:
+        m, v = torch.zeros(n), torch.zeros(n)
+    return p, g, m, v, targ
+
+
+# adam_t flat layout: two dense slabs and one conv slab with bias gaps; n
+# is no multiple of 256 and above 1024 * 256, so the kernel's grid-stride
+# loop (at most 1024 blocks of 256 threads) wraps for the first threads,
+# and the conv slab lies in the wrapped part.
+ADAM_T_N = 262144 + 777
+ADAM_T_DENSE = [(64, 70, 33), (64 + 70 * 33 + 70, 130, 257)]   # (off, N, K)
+ADAM_T_CONV = (262400, (5, 3, 2, 3))                 # (off, [OC,IC,kh,kw])

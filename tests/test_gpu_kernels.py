@@ -430,14 +430,17 @@ def test_graph_opt_direct_wgrad_and_wt_cache():
 @pytest.mark.parametrize("shapes", [
     # batch-64 phase table (rn=rk=1 everywhere)
     [(64, 256, 279), (64, 256, 256), (64, 1, 256)],
-    # large-batch: 128x128 sub-tiled blocks (rn/rk=2) incl. odd K and a
-    # width-1 problem in the same launch
+    # large-batch: split-M slabs of the 64x64 body incl. odd K and a
+    # width-1 problem in the same launch.  (rn/rk stay 1 here: the
+    # 128x128 sub-tiled body needs bf16 mode and TAC_AMD_WGRAD_RNRK=1,
+    # see test_gpu_wgrad.py::test_mwgrad_het_env_variants.)
     [(2048, 256, 393), (2048, 256, 256), (2048, 1, 256), (2048, 17, 256)],
 ])
 @pytest.mark.parametrize("mask", [False, True])
 def test_mwgrad_het_parity(ext, shapes, mask):
-    """Phase-wide heterogeneous wgrad launch (incl. the 2D sub-tiled
-    large-M path) vs plain dY^T @ X per problem."""
+    """Phase-wide heterogeneous wgrad launch in fp32 mode (64x64 body,
+    un-split and split-M) vs plain dY^T @ X per problem.  It does not
+    reach the 128x128 sub-tiled body."""
     torch.manual_seed(5)
     dys, ymasks, xs, dws, dbs = [], [], [], [], []
     Ms, Ns, Ks, lddys, ldxs, offs = [], [], [], [], [], []

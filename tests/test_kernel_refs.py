@@ -1,9 +1,12 @@
 """CPU check of the precondition behind the exact GPU kernel tests
-(test_gpu_mgemm.py, test_gpu_conv_exact.py): for the integer operands of
-every case table, the float64 reference is integer-valued and both
-max|ref| and the absolute-value contraction sum|a||b| stay below 2^24.
-Then every partial sum any kernel can form, in fp32 or from bf16-rounded
-operands, is exact, and bit equality is the right assertion."""
+(test_gpu_mgemm.py, test_gpu_conv_exact.py, test_gpu_wgrad.py): for the
+integer operands of every case table, the float64 reference is
+integer-valued and both max|ref| and the absolute-value contraction
+sum|a||b| stay below 2^24.  Then every partial sum any kernel can form,
+in fp32 or from bf16-rounded operands, is exact, and bit equality is the
+right assertion.  Also asserts the launch plans the wgrad case tables are
+listed with, and that a plain fp32 evaluation of Adam stays within half
+of the bounds the GPU Adam tests assert (test_gpu_adam_t.py)."""
 
 import pytest
 import torch
@@ -102,6 +105,237 @@ def test_trunk_case_is_exact(case):
     # ... and everything still fits the kernel's 40960-float LDS plan
     assert x.numel() + acts[0][0].numel() + acts[1][0].numel() <= 40960
     assert float(acts[2][0].abs().max()) > 0
+
+
+# ---------------------------------------------------------------------------
+# dense wgrad
+# ---------------------------------------------------------------------------
+
+def _check_wgrad_ops_exact(name, ops):
+    for z, o in enumerate(ops):
+        p = o.prob
+        _check_bf16_exact(name, o.dy, o.x)
+        dw, db, s_dw, s_db = kr.wgrad_ref(o.dy_v, o.x_v, o.mask_v)
+        _check_exact(f"{name}[{z}] dw", dw, s_dw)
+        _check_exact(f"{name}[{z}] db", db, s_db)
+        dw16, db16, _, _ = kr.wgrad_ref(o.dy_v, o.x_v, o.mask_v, bf16=True)
+        assert torch.equal(dw, dw16) and torch.equal(db, db16)
+        assert float(dw.abs().max()) > 0 and float(db.abs().max()) > 0
+        # the layout fits its storage
+        assert p.ld_dy >= p.N and p.x_off + p.K <= p.ld_x
+        assert o.dy.shape == (p.M, p.ld_dy) and o.x.shape == (p.M, p.ld_x)
+        assert (o.mask is not None) == p.mask
+        if p.mask:
+            assert o.mask.shape == o.dy.shape
+            vals = set(o.mask_v.unique().tolist())
+            assert vals == {-1.0, 0.0, 1.0}, (name, vals)
+
+
+@pytest.mark.parametrize("case", kr.MWGRAD_CASES, ids=lambda c: c.name)
+def test_mwgrad_cases_are_exact(case):
+    assert 1 <= case.nz <= 2 and len(case.bias) == case.nz
+    _check_wgrad_ops_exact(case.name, kr.wgrad_operands(case.problems, "int"))
+
+
+@pytest.mark.parametrize("case", kr.MWGRAD_HET_CASES, ids=lambda c: c.name)
+def test_mwgrad_het_cases_are_exact(case):
+    assert 1 <= len(case.problems) <= 12
+    _check_wgrad_ops_exact(case.name, kr.wgrad_operands(case.problems, "int"))
+
+
+@pytest.mark.parametrize("case", kr.MWGRAD_CASES, ids=lambda c: c.name)
+def test_mwgrad_cases_reach_their_path(case):
+    """The host plan of fused.hip::mwgrad, recomputed, is the one each
+    case is listed with, in both compute dtypes."""
+    for bf16, want in zip((False, True), case.expect):
+        split, m_chunk, chunks, tiles = kr.mwgrad_plan(
+            case.M, case.N, case.K, case.nz, bf16)
+        last = case.M - (split - 1) * m_chunk
+        assert 1 <= last <= m_chunk
+        if want == "split":
+            assert split > 1
+        elif want is not None:
+            assert (split, last) == want, (case.name, bf16, split, last)
+    bk32, bk16 = 16, 64
+    if case.name == "unsplit_multi_step":
+        for bf16, steps in ((False, 9), (True, 3)):
+            split, m_chunk, chunks, tiles = kr.mwgrad_plan(
+                case.M, case.N, case.K, case.nz, bf16)
+            assert (split, chunks, tiles) == (1, steps, 384)
+        assert case.M % bk16 == 2 and case.M % bk32 == 2
+    if case.name == "interior_strided":
+        # bf16 float4 staging: whole 64x64 tiles exist on both operands,
+        # strides are multiples of 4 and the x offset is 16-byte aligned
+        assert case.M >= 64 and case.N >= 64 and case.K >= 64
+        assert case.lddy % 4 == 0 and case.ldx % 4 == 0
+        assert case.x_off % 4 == 0 and case.mask
+    if case.name == "edge_strided":
+        assert case.x_off % 2 == 1 and case.N < 64 and case.K < 64
+    if case.name == "nobias_mixed":
+        assert set(case.bias) == {True, False}
+
+
+@pytest.mark.parametrize("case", kr.MWGRAD_HET_CASES, ids=lambda c: c.name)
+def test_mwgrad_het_cases_reach_their_path(case):
+    """The plan of mwgrad_het_impl / het_split, recomputed, in both dtypes
+    and under the XCD-clustered enumeration and the 128x128 sub-tiling."""
+    probs = case.problems
+    for bf16 in (False, True):
+        for xcd in (False, True):
+            for rnrk in (False, True):
+                plan = kr.het_plan(probs, bf16, xcd, rnrk)
+                want = kr.HET_PLANS.get((case.name, bf16, xcd, rnrk))
+                if want is not None:
+                    assert plan == want, (case.name, bf16, xcd, rnrk, plan)
+                split, m_chunk, chunks, blk = plan
+                assert 1 <= split <= 64 and split * m_chunk >= \
+                    max(p.M for p in probs) > (split - 1) * m_chunk
+                tiles = kr.het_tiles(probs, bf16, xcd, rnrk)
+                if not (rnrk and bf16):
+                    assert all(t[:2] == (1, 1) for t in tiles)
+    for bf16 in (False, True):
+        assert (case.name, bf16, False, False) in kr.HET_PLANS
+    if case.name == "phase64":
+        assert any(p.mask for p in probs) and any(p.ldx for p in probs)
+        assert kr.het_plan(probs, True)[:3:2] == (1, 1)   # one K-step
+    if case.name == "mixed_m":
+        split, m_chunk, _, _ = kr.het_plan(probs, False)
+        # the shallow problem ends inside the first slab
+        assert min(p.M for p in probs) <= m_chunk and split > 2
+    if case.name == "xcd_pad":
+        for bf16 in (False, True):
+            lin = kr.het_plan(probs, bf16)[3]
+            clu = kr.het_plan(probs, bf16, xcd=True)[3]
+            assert (lin, clu) == (31, 33)
+            assert clu > lin and clu % 8 != 0       # grid padded past it
+            assert (clu + 7) // 8 * 8 == 40
+        # odd tile counts on both axes of one problem
+        assert any(t[2] % 2 == 1 and t[2] > 1
+                   for t in kr.het_tiles(probs, False, True))
+    if case.name == "big":
+        tiles = kr.het_tiles(probs, True, False, True)
+        # every (rn, rk) the 128x128 body runs with ((1, 1) is the 64x64
+        # body, which the other cases cover)
+        assert {t[:2] for t in tiles} == {(1, 2), (2, 1), (2, 2)}
+        assert all(p.M >= 1024 for p in probs)
+        for key in ((True, False, False), (True, False, True)):
+            split, m_chunk, _, _ = kr.het_plan(probs, *key)
+            assert probs[0].M - (split - 1) * m_chunk == 6
+    if case.name == "many_tiles":
+        assert len(probs) == 12
+        assert kr.het_plan(probs, False)[3] == 384
+        assert {p.mask for p in probs} == {True, False}
+
+
+def test_wgrad_case_table_properties():
+    """The wgrad tables keep the properties they were chosen for."""
+    plans = [(c, bf16, kr.mwgrad_plan(c.M, c.N, c.K, c.nz, bf16))
+             for c in kr.MWGRAD_CASES for bf16 in (False, True)]
+    # a last slab of one row
+    assert any(s > 1 and c.M - (s - 1) * mc == 1
+               for c, _, (s, mc, _, _) in plans)
+    assert any(c.N == 1 for c in kr.MWGRAD_CASES)
+    assert any(p.N == 1 for h in kr.MWGRAD_HET_CASES for p in h.problems)
+    assert any(c.lddy and c.lddy % 4 == 0 and c.N >= 64
+               for c in kr.MWGRAD_CASES)
+    assert any(len({p.M for p in h.problems}) > 1
+               for h in kr.MWGRAD_HET_CASES)
+    assert any(not p.bias for h in kr.MWGRAD_HET_CASES for p in h.problems)
+    # rounding_bound's +32 term is what covers the slab combine
+    for name in kr.MWGRAD_ROUNDING_CASES:
+        c = kr.mwgrad_case(name)
+        for bf16 in (False, True):
+            assert kr.mwgrad_plan(c.M, c.N, c.K, c.nz, bf16)[0] <= 32
+    for name in kr.MWGRAD_HET_ROUNDING_CASES:
+        for bf16 in (False, True):
+            assert kr.het_plan(kr.het_case(name).problems, bf16)[0] <= 32
+    # no interior-path case with an odd x offset: no caller produces one
+    for probs in [c.problems for c in kr.MWGRAD_CASES] + \
+            [h.problems for h in kr.MWGRAD_HET_CASES]:
+        for p in probs:
+            if p.ld_x % 4 == 0 and p.K >= 64 and p.M >= 64:
+                assert p.x_off % 4 == 0, p
+
+
+# ---------------------------------------------------------------------------
+# Adam
+# ---------------------------------------------------------------------------
+
+def _fma32(a, b, c):
+    """fmaf on fp32 tensors: the product of two fp32 values is exact in
+    float64, so one float64 add and one rounding to fp32 follow."""
+    return (a.double() * b.double() + c.double()).float()
+
+
+def adam_emulate_fp32(p, g, m, v, targ, t, hyper):
+    """adam_math / polyak_math of fused.hip in CPU fp32 tensor ops, in
+    the order the kernel writes them."""
+    f = {k: torch.tensor(x, dtype=torch.float32) for k, x in hyper.items()}
+    one = torch.tensor(1.0)
+    tt = torch.tensor(float(t))
+    bc1 = one - torch.pow(f["b1"], tt)
+    bc2 = one - torch.pow(f["b2"], tt)
+    gi = _fma32(f["wd"], p, g)
+    mi = _fma32(f["b1"], m, (one - f["b1"]) * gi)
+    vi = _fma32(f["b2"], v, ((one - f["b2"]) * gi) * gi)
+    pn = p - f["lr"] / bc1 * mi / (torch.sqrt(vi / bc2) + f["eps"])
+    tn = None
+    if targ is not None:
+        tn = f["rho"] * targ + (one - f["rho"]) * pn
+    assert pn.dtype == torch.float32 and vi.dtype == torch.float32
+    return pn, mi, vi, tn
+
+
+@pytest.mark.parametrize("wd", [0.0, 2.0 ** -7])
+@pytest.mark.parametrize("step", [1, 2, 1000])
+def test_adam_fp32_emulation_within_half_bounds(step, wd):
+    """The bounds the GPU Adam tests assert are fair: a plain fp32
+    evaluation in the kernel's order stays under HALF of each."""
+    hyper = dict(kr.ADAM_HYPER, wd=wd)
+    p, g, m, v, targ = kr.adam_state(20000, step, True, seed=step)
+    assert float(g.abs().min()) >= 0.99e-6 and float(g.abs().max()) <= 10.0
+    assert float(g.abs().min()) < 1e-5 and float(g.abs().max()) > 1.0
+    assert float(p.abs().max()) <= 1 / 16 and float(targ.abs().max()) <= 1 / 16
+    assert (step == 1) == (float(m.abs().max()) == 0.0)
+    ref = kr.adam_ref(p, g, m, v, targ, step, hyper)
+    bounds = kr.adam_bounds(p, g, m, ref, hyper)
+    outs = adam_emulate_fp32(p, g, m, v, targ, step, hyper)
+    for nm, out, r, b in zip("pmvt", outs, ref, bounds):
+        ratio = float(((out.double() - r).abs() / b).max())
+        print(f"adam emulation step={step} wd={wd} {nm}: "
+              f"max err/bound = {ratio:.3f}")
+        assert ratio <= 0.5, (nm, ratio)
+    # the update is visible: a skipped element is off by |u| itself
+    u = ref[4]
+    assert float((u.abs() / bounds[0]).median()) > 1000
+    assert float((u.abs() / bounds[0]).min()) > 4
+
+
+def test_adam_ref_uses_fp32_hyperparameters():
+    """1 - b2 from the fp32-rounded 0.999 differs from the double's by
+    1.3e-5 relative: the reference must take the kernel's value."""
+    b2 = kr.f32_as_double(0.999)
+    assert abs((1 - b2) / (1 - 0.999) - 1) > 1e-5
+    p, g, m, v, _ = kr.adam_state(64, 2, False)
+    r32 = kr.adam_ref(p, g, m, v, None, 2, kr.ADAM_HYPER)
+    assert r32[3] is None
+    assert torch.equal(r32[2], b2 * v.double()
+                       + (1 - b2) * g.double() * g.double())
+
+
+def test_adam_t_layout_properties():
+    n = kr.ADAM_T_N
+    assert n % 256 != 0 and n > 1024 * 256
+    slabs = [(off, N * K) for off, N, K in kr.ADAM_T_DENSE]
+    off, (oc, ic, kh, kw) = kr.ADAM_T_CONV
+    slabs.append((off, oc * ic * kh * kw))
+    assert kh * kw == 6
+    at = 0
+    for off, sz in slabs:                  # sorted, with gaps, inside n
+        assert off > at
+        at = off + sz
+    assert at < n
+    assert slabs[-1][0] >= 1024 * 256      # in the grid-stride wrap
 
 
 def test_conv_geometry_table_properties():

@@ -2720,7 +2720,18 @@ void mwgrad(std::vector<torch::Tensor> dys,
             int64_t M, int64_t N, int64_t K, int64_t lddy, int64_t ldx,
             int64_t x_off) {
   const int nz = (int)dys.size();
+  // WGemm holds two problems; every list is indexed by z below
+  TORCH_CHECK(nz >= 1 && nz <= 2, "mwgrad: 1..2 problems, got ", nz);
+  TORCH_CHECK((int)xs.size() == nz && (int)dws.size() == nz
+              && (int)dbs.size() == nz,
+              "mwgrad: xs/dws/dbs must hold one entry per problem");
+  TORCH_CHECK(ymasks.empty() || (int)ymasks.size() == nz,
+              "mwgrad: ymasks must be empty or hold one entry per problem");
   const bool has_mask = ymasks.size() && ymasks[0].has_value();
+  // one MASK instantiation serves the whole launch
+  for (const auto& ym : ymasks)
+    TORCH_CHECK(ym.has_value() == has_mask,
+                "mwgrad: masks must be all present or all absent");
   WGemm g{};
   g.M = (int)M; g.N = (int)N; g.K = (int)K;
   g.lddy = (int)lddy; g.ldx = (int)ldx;
@@ -3325,10 +3336,28 @@ void adam_t(torch::Tensor p, torch::Tensor g, torch::Tensor m,
   ATArgs ta{};
   ta.n_layers = (int)offsets.size();
   TORCH_CHECK(ta.n_layers <= MAX_T);
+  TORCH_CHECK(wts.size() == offsets.size(),
+              "adam_t: one W^T cache per slab offset");
+  TORCH_CHECK(bss.empty() || bss.size() == offsets.size(),
+              "adam_t: bss must be empty or hold one entry per slab");
+  // the kernel's slab search stops at the first offset above the
+  // element: unsorted or overlapping slabs would leave a cache stale
+  int64_t slab_end = 0;
+  for (int i = 0; i < ta.n_layers; ++i) {
+    TORCH_CHECK(offsets[i] >= slab_end,
+                "adam_t: slab offsets must be strictly increasing and the "
+                "slabs must not overlap (slab ", i, ")");
+    slab_end = offsets[i] + wts[i].numel();
+    TORCH_CHECK(wts[i].numel() > 0 && slab_end <= p.numel(),
+                "adam_t: slab ", i, " does not lie inside [0, n)");
+  }
   for (int i = 0; i < ta.n_layers; ++i) {
     ta.off[i] = offsets[i];
     ta.wt[i] = wts[i].data_ptr<float>();
     ta.BS[i] = bss.empty() ? 1 : (int)bss[i];
+    TORCH_CHECK(wts[i].dim() == 2 && ta.BS[i] >= 1
+                && wts[i].size(1) % ta.BS[i] == 0,
+                "adam_t: W^T cache ", i, " must be [K, N * bs]");
     if (ta.BS[i] == 1) {
       ta.K[i] = (int)wts[i].size(0);   // dense: wt is [K, N]
       ta.N[i] = (int)wts[i].size(1);
