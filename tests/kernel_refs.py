@@ -1,8 +1,8 @@
 """Float64 CPU references, operand generators and case tables shared by
 test_gpu_mgemm.py, test_gpu_conv_exact.py, conv_lds_worker.py,
-test_gpu_wgrad.py, wgrad_env_worker.py, test_gpu_adam_t.py and the CPU
-precondition test (test_kernel_refs.py).  Plain helper module, not a
-conftest.
+test_gpu_wgrad.py, wgrad_env_worker.py, test_gpu_adam_t.py,
+test_gpu_philox.py, test_gpu_heads_losses.py and the CPU precondition test
+(test_kernel_refs.py).  Plain helper module, not a conftest.
 
 Two operand kinds:
  * "int":   small integers stored as fp32 (x, w, dy, rank-1 factors in
@@ -18,6 +18,9 @@ Two operand kinds:
 from dataclasses import dataclass, field
 from typing import List, Optional, Tuple
 
+import math
+
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -778,3 +781,559 @@ def adam_state(n, step, with_targ, seed=0, g=None):
 ADAM_T_N = 262144 + 777
 ADAM_T_DENSE = [(64, 70, 33), (64 + 70 * 33 + 70, 130, 257)]   # (off, N, K)
 ADAM_T_CONV = (262400, (5, 3, 2, 3))                 # (off, [OC,IC,kh,kw])
+
+
+# ---------------------------------------------------------------------------
+# Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2,
+# 3", SC'11) and the draws the kernels derive from it
+# ---------------------------------------------------------------------------
+#
+# One round maps the counter (c0, c1, c2, c3) under the key (k0, k1) to
+#     (hi(M1 * c2) ^ c1 ^ k0,  lo(M1 * c2),  hi(M0 * c0) ^ c3 ^ k1,
+#      lo(M0 * c0))
+# with the 32x32 -> 64 bit products split into high and low words; after
+# every round the key advances by the Weyl constants (W0, W1).  Ten rounds.
+
+PHILOX_M0, PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+PHILOX_W0, PHILOX_W1 = 0x9E3779B9, 0xBB67AE85     # golden ratio, sqrt(3) - 1
+_M32 = 0xFFFFFFFF
+_M64 = 0xFFFFFFFFFFFFFFFF
+NOISE_KEY = 0x517CC1B727220A95     # xor-ed into the seed by the noise draws
+
+
+def as_i64(v):
+    """A 64-bit pattern as the signed integer an int64 argument takes."""
+    v &= _M64
+    return v - (1 << 64) if v >> 63 else v
+
+
+def philox4x32(seed, chi, clo, rounds=10):
+    """Philox4x32 on Python ints.  The kernels' packing: counter words
+    c0, c1 = low, high of clo; c2, c3 = low, high of chi; key words
+    k0, k1 = low, high of seed.  Returns the four output words."""
+    seed, chi, clo = seed & _M64, chi & _M64, clo & _M64
+    c0, c1, c2, c3 = clo & _M32, clo >> 32, chi & _M32, chi >> 32
+    k0, k1 = seed & _M32, seed >> 32
+    for _ in range(rounds):
+        p0, p1 = PHILOX_M0 * c0, PHILOX_M1 * c2
+        c0, c1, c2, c3 = ((p1 >> 32) ^ c1 ^ k0, p1 & _M32,
+                          (p0 >> 32) ^ c3 ^ k1, p0 & _M32)
+        k0, k1 = (k0 + PHILOX_W0) & _M32, (k1 + PHILOX_W1) & _M32
+    return c0, c1, c2, c3
+
+
+def philox4x32_np(seed, chi, clo, rounds=10):
+    """philox4x32 over an array of clo (any integer dtype; taken mod 2^64):
+    uint32 [n, 4].  Products of two 32-bit words fit uint64 exactly."""
+    seed, chi = seed & _M64, chi & _M64
+    clo = np.asarray(clo).astype(np.uint64)
+    m32, s32 = np.uint64(_M32), np.uint64(32)
+    c0, c1 = clo & m32, clo >> s32
+    c2 = np.full_like(c0, chi & _M32)
+    c3 = np.full_like(c0, chi >> 32)
+    k0, k1 = seed & _M32, seed >> 32
+    for _ in range(rounds):
+        p0, p1 = np.uint64(PHILOX_M0) * c0, np.uint64(PHILOX_M1) * c2
+        c0, c1, c2, c3 = ((p1 >> s32) ^ c1 ^ np.uint64(k0), p1 & m32,
+                          (p0 >> s32) ^ c3 ^ np.uint64(k1), p0 & m32)
+        k0, k1 = (k0 + PHILOX_W0) & _M32, (k1 + PHILOX_W1) & _M32
+    return np.stack([c0, c1, c2, c3], axis=-1).astype(np.uint32)
+
+
+def philox_rows(seed, chi, n, clo0=0):
+    """uint32 [n, 4]: the draws of subsequences clo0 .. clo0 + n - 1."""
+    clo = (np.arange(n, dtype=np.uint64) + np.uint64(clo0 & _M64))
+    return philox4x32_np(seed, chi, clo)
+
+
+def uniform32(word):
+    """(float32(word) + 1f) * 2^-32 in fp32, as the kernels map a word to
+    (0, 1]: the conversion rounds to nearest even, so 0xffffffff gives 1."""
+    w = np.asarray(word, dtype=np.uint32).astype(np.float32)
+    return (w + np.float32(1.0)) * np.float32(2.0 ** -32)
+
+
+def box_muller64(u0, u1):
+    """float64 (R cos, R sin, R) with R = sqrt(-2 ln u0), angle 2 pi u1,
+    on fp32 uniforms widened to float64."""
+    u0 = np.asarray(u0, dtype=np.float32).astype(np.float64)
+    u1 = np.asarray(u1, dtype=np.float32).astype(np.float64)
+    r = np.sqrt(-2.0 * np.log(u0))
+    return r * np.cos(2.0 * np.pi * u1), r * np.sin(2.0 * np.pi * u1), r
+
+
+def box_muller32(u0, u1):
+    """The same formula evaluated in numpy fp32: (R cos, R sin)."""
+    u0 = np.asarray(u0, dtype=np.float32)
+    u1 = np.asarray(u1, dtype=np.float32)
+    r = np.sqrt(np.float32(-2.0) * np.log(u0))
+    ang = np.float32(6.283185307179586) * u1
+    return r * np.cos(ang), r * np.sin(ang)
+
+
+NOISE_CAP = 5e-5     # |eps_kernel - eps64| <= NOISE_CAP * max(1, R)
+
+
+def draw_index(x, y, size):
+    """((x << 32) | y) % size: the replay slot of one draw (ints or
+    arrays; int64 out for arrays)."""
+    if isinstance(x, (int, np.integer)) and isinstance(y, (int, np.integer)):
+        return ((int(x) << 32) | int(y)) % int(size)
+    u = (np.asarray(x).astype(np.uint64) << np.uint64(32)) \
+        | np.asarray(y).astype(np.uint64)
+    return (u % np.uint64(size)).astype(np.int64)
+
+
+def draw_shifts(z, w, pad):
+    """[..., 4] signed shifts (dy_s, dx_s, dy_n, dx_n) in -pad..pad, the
+    order visual_gather_shift_kernel documents: z is the state frame's
+    word, w the next-state frame's, 16 bits per axis (high half = y) mod
+    2 pad + 1.  VisualBatch.shifts holds these plus pad."""
+    z = np.asarray(z).astype(np.int64)
+    w = np.asarray(w).astype(np.int64)
+    span = 2 * pad + 1
+    return np.stack([(z >> 16) % span - pad, (z & 0xffff) % span - pad,
+                     (w >> 16) % span - pad, (w & 0xffff) % span - pad],
+                    axis=-1)
+
+
+def per_targets(x, root, B):
+    """The stratified targets of per_sample in numpy fp32, no contraction:
+    u_j = (j + (x_j >> 8) * 2^-24) * (root / B)."""
+    x = np.asarray(x, dtype=np.uint32)
+    u01 = (x >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
+    seg = np.float32(root) / np.float32(B)
+    return (np.arange(B, dtype=np.float32) + u01) * seg
+
+
+def noise_eps64(seed, ctr, R, A):
+    """float64 [R, A] noise of tg_fwd2 / tg_eps and its Box-Muller radius:
+    element (b, a) draws philox(seed ^ NOISE_KEY, ctr, b * A + a) and uses
+    words x, y."""
+    w = philox_rows(seed ^ NOISE_KEY, ctr, R * A)
+    c, _, r = box_muller64(uniform32(w[:, 0]), uniform32(w[:, 1]))
+    return c.reshape(R, A), r.reshape(R, A)
+
+
+def noise_eps32(seed, ctr, R, A):
+    """The same draw through the fp32 formula: fp32 tensor [R, A]."""
+    w = philox_rows(seed ^ NOISE_KEY, ctr, R * A)
+    c, _ = box_muller32(uniform32(w[:, 0]), uniform32(w[:, 1]))
+    return torch.from_numpy(c.reshape(R, A).astype(np.float32))
+
+
+# ---------------------------------------------------------------------------
+# SAC head, loss and temperature kernels (fused.hip: tg_fwd2, tg_bwd2,
+# qloss2, piloss2, alpha_update)
+# ---------------------------------------------------------------------------
+#
+# Every reference is float64 on the fp32 inputs with scalars and literals
+# taken as the kernel holds them (fp32, widened).  Every bound is first
+# order and summed over the operations: a rounded fp32 operation can be
+# off by E32 = 2^-24 of the magnitude of its result and is charged
+# U = 2 E32; an input's bound is carried through by the magnitude of the
+# partial derivative; a libm call f contributes tol[f] relative
+# (LIBM_FLOOR on the CPU; on the GPU 4x the measured error of torch's own
+# fp32 op, never below the floor); a reduction goes through
+# rounding_bound(), which carries its own factor of two.  The factor of
+# two in U is what the fairness condition needs: an output that is one or
+# two rounded operations on exact inputs reaches the worst case of a
+# 2^-24 charge routinely, and a correct fp32 evaluation has to stay under
+# HALF the bound (test_kernel_refs.py holds every *_f32 function below,
+# the plain fp32 evaluation in the kernel's order, to that).
+
+E32 = 2.0 ** -24
+U = 2.0 * E32
+LIBM_FLOOR = 2.0 ** -22
+LIBM_TOL = dict(exp=LIBM_FLOOR, tanh=LIBM_FLOOR, log1p=LIBM_FLOOR)
+LOG_2PI_F = f32_as_double(1.8378770664093453)
+TWO_LN2_F = f32_as_double(1.3862943611198906)
+
+TG_ACT_LIMIT, TG_LO, TG_HI = 2.5, -5.0, 2.0
+# (R, A, B0, ld0, col0, ld1, col1)
+TG_CASES = [
+    (2, 1, 1, 3, 1, 2, 0),
+    (6, 6, 3, 23, 17, 23, 17),
+    (5, 17, 5, 20, 3, 17, 0),          # nothing goes to out1
+    (4, 64, 0, 64, 0, 70, 5),          # everything goes to out1
+    (130, 33, 64, 40, 7, 50, 0),
+]
+TG_MU = (-12.0, -3.0, 0.0, 0.5, 12.0)
+TG_SEED, TG_CTR = 11, 41           # noise key and device counter
+
+
+def tg_id(case):
+    return "x".join(str(v) for v in case)
+
+
+def tg_raw_log_std():
+    """The raw log_std values every case cycles through: below, at and
+    just inside both clamp ends, one interior value, beyond the top."""
+    lo = torch.tensor(TG_LO)
+    hi = torch.tensor(TG_HI)
+    inf = torch.tensor(float("inf"))
+    return [TG_LO - 1.0, TG_LO, float(torch.nextafter(lo, inf)), -1.25,
+            TG_HI, float(torch.nextafter(hi, -inf)), TG_HI + 3.0]
+
+
+def tg_hl(case):
+    """fp32 hl [R, 2A] = mu | raw log_std.  Seven of every nine elements
+    take the next special log_std, five of every eight the next special
+    mu (periods 9 and 8 are coprime, so all pairs occur); the rest are
+    general floats.  Offsets differ per case so the small cases cover the
+    list between them."""
+    R, A = case[:2]
+    g = _gen(7000 + R * 100 + A)
+    i = torch.arange(R * A) + R + A
+    mu = torch.randn(R * A, generator=g) * 2
+    ls = torch.rand(R * A, generator=g) * 5 - 4
+    sp_mu = torch.tensor(TG_MU)
+    sp_ls = torch.tensor(tg_raw_log_std())
+    km, kl = i % 8, i % 9
+    mu = torch.where(km < 5, sp_mu[km.clamp_max(4)], mu)
+    ls = torch.where(kl < 7, sp_ls[kl.clamp_max(6)], ls)
+    return torch.cat([mu.view(R, A), ls.view(R, A)], 1).contiguous()
+
+
+def tg_ref(hl, eps, act_limit, lo, hi):
+    """float64 (pi, prob, logp) of the tanh-Gaussian head on hl = mu |
+    raw log_std and the noise eps.  The Jacobian term is the reference
+    project's 2 ln 2 - prob - softplus(-2 prob) as it stands (see
+    DEVIATIONS.md)."""
+    A = hl.shape[1] // 2
+    al, lo, hi = (f32_as_double(v) for v in (act_limit, lo, hi))
+    mu, raw = hl[:, :A].double(), hl[:, A:].double()
+    eps = eps.double()
+    ls = raw.clamp(lo, hi)
+    prob = mu + ls.exp() * eps
+    pi = prob.tanh() * al
+    sp = torch.logaddexp(torch.zeros_like(prob), -2.0 * prob)
+    gauss = -0.5 * eps * eps - ls - 0.5 * LOG_2PI_F
+    corr = TWO_LN2_F - prob - sp
+    return pi, prob, (gauss - corr).sum(1)
+
+
+def tg_fwd_bounds(hl, eps, act_limit, lo, hi, tol=LIBM_TOL):
+    """Elementwise bounds (pi, prob, logp) on |kernel - tg_ref|."""
+    A = hl.shape[1] // 2
+    al, lo, hi = (f32_as_double(v) for v in (act_limit, lo, hi))
+    mu, raw = hl[:, :A].double(), hl[:, A:].double()
+    eps = eps.double()
+    ls = raw.clamp(lo, hi)
+    se = ls.exp() * eps
+    prob = mu + se
+    b_prob = (tol["exp"] + U) * se.abs() + U * prob.abs()
+    t = prob.tanh()
+    b_pi = al * (tol["tanh"] * t.abs() + (1 - t * t) * b_prob) \
+        + U * (al * t).abs()
+    # logp: gauss = ((-eps^2/2) - ls) - log(2 pi)/2, three roundings
+    a1 = 0.5 * eps * eps
+    a2 = -a1 - ls
+    gauss = a2 - 0.5 * LOG_2PI_F
+    b_gauss = U * (a1 + a2.abs() + gauss.abs())
+    # softplus(x), x = -2 prob: d/dx = sigmoid(x); exp's relative error
+    # enters log1p through y / (1 + y) = sigmoid(x); above x = 20 the
+    # kernel returns x, short of the truth by log1p(exp(-x)) < 2.1e-9
+    x = -2.0 * prob
+    sig = torch.sigmoid(x)
+    sp = torch.logaddexp(torch.zeros_like(x), x)
+    b_sp = 2 * sig * b_prob + tol["exp"] * sig + tol["log1p"] * sp \
+        + 2.1e-9 * (x > 20) + 1e-37
+    c1 = TWO_LN2_F - prob
+    corr = c1 - sp
+    b_corr = b_prob + U * c1.abs() + b_sp + U * corr.abs()
+    term = gauss - corr
+    b_term = b_gauss + b_corr + U * term.abs()
+    b_logp = b_term.sum(1) + rounding_bound(A, term.abs().sum(1))
+    return b_pi, b_prob, b_logp
+
+
+def tg_fwd_f32(hl, eps, act_limit, lo, hi):
+    """Plain fp32 (pi, prob, logp) in tg_fwd2_kernel's order."""
+    A = hl.shape[1] // 2
+    f = lambda v: torch.tensor(v, dtype=torch.float32)
+    mu, raw = hl[:, :A], hl[:, A:]
+    ls = raw.clamp(float(f(lo)), float(f(hi)))
+    prob = mu + ls.exp() * eps
+    pi = prob.tanh() * f(act_limit)
+    x = -2.0 * prob
+    sp = torch.where(x > 20.0, x, torch.log1p(torch.exp(x.clamp_max(20.0))))
+    gauss = -0.5 * eps * eps - ls - f(0.5) * f(1.8378770664093453)
+    corr = f(1.3862943611198906) - prob - sp
+    return pi, prob, (gauss - corr).sum(1)
+
+
+def tg_bwd_operands(case, B):
+    """fp32 (dxc, dxc2) slabs [B, ld0] for the backward of a TG case: the
+    gradient columns are [col0, col0 + A) with col0 > 0 (ld0 and a column
+    offset of at least 1 are taken from the forward case)."""
+    R, A, _, ld0, col0 = case[:5]
+    g = _gen(7100 + R * 100 + A)
+    return (torch.randn(B, ld0 + 1, generator=g),
+            torch.randn(B, ld0 + 1, generator=g), col0 + 1)
+
+
+def tg_bwd_rows(case):
+    """Rows the backward runs over: the out0 rows, or all when B0 = 0."""
+    return case[2] if case[2] > 0 else case[0]
+
+
+def tg_bwd_ref(hl, prob, dpi_a, dpi_b, alpha, B, act_limit, lo, hi):
+    """float64 (dmu, dls) of tg_bwd2 over rows :B.  dpi_a / dpi_b are the
+    logical [B, A] gradient blocks (dpi_b may be None), prob the fp32
+    pre-squash sample the forward stored, alpha / B the seed of logp."""
+    A = hl.shape[1] // 2
+    al, lo, hi, alpha = (f32_as_double(v) for v in (act_limit, lo, hi, alpha))
+    mu, raw = hl[:B, :A].double(), hl[:B, A:].double()
+    p = prob[:B].double()
+    t = p.tanh()
+    se = p - mu
+    dpi = dpi_a.double() + (dpi_b.double() if dpi_b is not None else 0.0)
+    dl = alpha / B
+    dp = dpi * al * (1 - t * t)
+    g_mu = dp + dl * t
+    g_ls = dp * se + dl * (se * t - 1.0)
+    mask = (raw >= lo) & (raw <= hi)
+    return g_mu, g_ls * mask
+
+
+def tg_bwd_bounds(hl, prob, dpi_a, dpi_b, alpha, B, act_limit, lo, hi,
+                  tol=LIBM_TOL):
+    """Elementwise bounds (dmu, dls).  dp = dpi * act_limit * (1 - t^2)
+    cancels to zero at saturation, so its error is carried as an absolute
+    one: t's error times 2|t|, plus the roundings of t^2 and of 1 - t^2."""
+    A = hl.shape[1] // 2
+    al, alpha = f32_as_double(act_limit), f32_as_double(alpha)
+    mu = hl[:B, :A].double()
+    p = prob[:B].double()
+    t = p.tanh()
+    b_t = tol["tanh"] * t.abs()
+    se = p - mu
+    b_se = U * se.abs()
+    dpi = dpi_a.double() + (dpi_b.double() if dpi_b is not None else 0.0)
+    b_dpi = U * dpi.abs() if dpi_b is not None else torch.zeros_like(dpi)
+    dl = alpha / B
+    b_dl = U * dl
+    om = 1 - t * t
+    b_om = 2 * t.abs() * b_t + U * t * t + U * om
+    dp = dpi * al * om
+    b_dp = (dpi * al).abs() * b_om + al * om * b_dpi + U * dp.abs()
+    g_mu = dp + dl * t
+    b_mu = b_dp + t.abs() * b_dl + dl * b_t + U * (dl * t).abs() \
+        + U * g_mu.abs()
+    inner = se * t - 1.0
+    b_in = t.abs() * b_se + se.abs() * b_t + U * (se * t).abs() \
+        + U * inner.abs()
+    g_ls = dp * se + dl * inner
+    b_ls = se.abs() * b_dp + dp.abs() * b_se + U * (dp * se).abs() \
+        + dl * b_in + inner.abs() * b_dl + U * (dl * inner).abs() \
+        + U * g_ls.abs()
+    return b_mu + 1e-37, b_ls + 1e-37
+
+
+def tg_bwd_f32(hl, prob, dpi_a, dpi_b, alpha, B, act_limit, lo, hi):
+    """Plain fp32 (dmu, dls) in tg_bwd2_kernel's order."""
+    A = hl.shape[1] // 2
+    f = lambda v: torch.tensor(v, dtype=torch.float32)
+    mu, raw = hl[:B, :A], hl[:B, A:]
+    p = prob[:B]
+    t = p.tanh()
+    se = p - mu
+    dpi = dpi_a + dpi_b if dpi_b is not None else dpi_a
+    dl = f(alpha) / f(float(B))
+    dp = dpi * f(act_limit) * (1.0 - t * t)
+    g_mu = dp + dl * t
+    g_ls = dp * se + dl * (se * t - 1.0)
+    mask = ((raw >= f(lo)) & (raw <= f(hi))).float()
+    return g_mu, g_ls * mask
+
+
+# ---- qloss2 (unweighted) and piloss2 ---------------------------------------
+
+LOSS_B_FUSED = [1, 63, 64, 65, 255, 257, 1000, 1024]
+LOSS_B_UNFUSED = 1500
+LOSS_H2 = [1, 24]
+LOSS_ACC0 = 3.0
+QLOSS_HYPER = dict(alpha=0.2, gamma=0.99, scale=1.7)
+
+
+def qloss_inputs(B, h2, seed=0):
+    """General (non-dyadic) fp32 operands; done holds both values."""
+    g = _gen(8000 + 7 * B + h2 + seed)
+    r = lambda *s: torch.randn(*s, generator=g)
+    done = (torch.rand(B, generator=g) < 0.3).float()
+    done[0] = 0.0
+    done[-1] = 1.0 if B > 1 else 0.0
+    return dict(q1=r(B) * 3, q2=r(B) * 3, q1t=r(B) * 3, q2t=r(B) * 3,
+                logp=r(B) * 4 - 2, rew=r(B), done=done,
+                wt0=r(max(h2, 1)), wt1=r(max(h2, 1)))
+
+
+def qloss_ref(t, B, alpha, gamma, scale):
+    """float64 dict(loss, dq1, dq2, dy0, dy1) of the unweighted qloss2 and
+    the matching bounds dict, from the fp32 operands t."""
+    alpha, gamma, scale = (f32_as_double(v) for v in (alpha, gamma, scale))
+    d = {k: v.double() for k, v in t.items()}
+    t1 = scale * d["rew"]
+    t2 = alpha * d["logp"]
+    mn = torch.min(d["q1t"], d["q2t"])
+    t3 = mn - t2
+    gd = gamma * (1.0 - d["done"])
+    t4 = gd * t3
+    backup = t1 + t4
+    b_t3 = U * (t2.abs() + t3.abs())
+    b_t4 = U * t4.abs() + gd * b_t3 + U * gd * t3.abs()
+    b_bk = U * (t1.abs() + backup.abs()) + b_t4
+    ref, bnd = {}, {}
+    s = torch.zeros(B, dtype=torch.float64)
+    b_s = torch.zeros(B, dtype=torch.float64)
+    for z, q in ((0, "q1"), (1, "q2")):
+        e = d[q] - backup
+        b_e = U * e.abs() + b_bk
+        gq = 2.0 * e / B
+        b_g = 2.0 * b_e / B + U * gq.abs()
+        w = d[f"wt{z}"]
+        ref[f"dq{z + 1}"], bnd[f"dq{z + 1}"] = gq, b_g + 1e-37
+        ref[f"dy{z}"] = gq[:, None] * w[None]
+        bnd[f"dy{z}"] = w.abs()[None] * b_g[:, None] \
+            + U * ref[f"dy{z}"].abs() + 1e-37
+        s = s + e * e
+        b_s = b_s + 2 * e.abs() * b_e + U * e * e
+    b_s = b_s + U * s
+    ref["loss"] = s.sum() / B
+    bnd["loss"] = (b_s.sum() + rounding_bound(B, s.sum())) / B \
+        + U * ref["loss"]
+    return ref, bnd
+
+
+def qloss_f32(t, B, alpha, gamma, scale):
+    """Plain fp32 evaluation in qloss2_kernel's order."""
+    f = lambda v: torch.tensor(v, dtype=torch.float32)
+    backup = f(scale) * t["rew"] + f(gamma) * (1.0 - t["done"]) * (
+        torch.min(t["q1t"], t["q2t"]) - f(alpha) * t["logp"])
+    e1, e2 = t["q1"] - backup, t["q2"] - backup
+    g1, g2 = 2.0 * e1 / float(B), 2.0 * e2 / float(B)
+    return dict(loss=(e1 * e1 + e2 * e2).sum() / float(B), dq1=g1, dq2=g2,
+                dy0=g1[:, None] * t["wt0"][None],
+                dy1=g2[:, None] * t["wt1"][None])
+
+
+def piloss_inputs(B, h2, seed=0):
+    """Rows 0, 3, 6, ... have q1 == q2 exactly, rows 1, 4, ... q1 < q2,
+    rows 2, 5, ... q2 < q1."""
+    g = _gen(9000 + 7 * B + h2 + seed)
+    r = lambda *s: torch.randn(*s, generator=g)
+    q1 = r(B) * 3
+    gap = torch.rand(B, generator=g) + 0.01
+    k = torch.arange(B) % 3
+    q2 = torch.where(k == 0, q1, torch.where(k == 1, q1 + gap, q1 - gap))
+    return dict(q1=q1, q2=q2, logp=r(B) * 4 - 2, wt0=r(max(h2, 1)),
+                wt1=r(max(h2, 1)))
+
+
+def piloss_ref(t, B, alpha):
+    """float64 dict(loss, mean_logp, dq1, dq2, dy0, dy1) of piloss2 and the
+    matching bounds dict.  The seeds -1/B and -0.5/B are one correctly
+    rounded division each."""
+    alpha = f32_as_double(alpha)
+    d = {k: v.double() for k, v in t.items()}
+    a, b, lp = d["q1"], d["q2"], d["logp"]
+    t1 = alpha * lp
+    el = t1 - torch.min(a, b)
+    b_el = U * (t1.abs() + el.abs())
+    ref, bnd = {}, {}
+    ref["loss"] = el.sum() / B
+    bnd["loss"] = (b_el.sum() + rounding_bound(B, el.abs().sum())) / B \
+        + U * ref["loss"].abs()
+    ref["mean_logp"] = lp.sum() / B
+    bnd["mean_logp"] = rounding_bound(B, lp.abs().sum()) / B \
+        + U * ref["mean_logp"].abs()
+    tie = a == b
+    g1 = torch.where(tie, -0.5, torch.where(a < b, -1.0, 0.0)) / B
+    g2 = torch.where(tie, -0.5, torch.where(b < a, -1.0, 0.0)) / B
+    for z, gq in ((0, g1), (1, g2)):
+        w = d[f"wt{z}"]
+        ref[f"dq{z + 1}"], bnd[f"dq{z + 1}"] = gq, U * gq.abs()
+        ref[f"dy{z}"] = gq[:, None] * w[None]
+        bnd[f"dy{z}"] = 2 * U * ref[f"dy{z}"].abs()
+    return ref, bnd
+
+
+def piloss_f32(t, B, alpha):
+    """Plain fp32 evaluation in piloss2_kernel's order."""
+    f = lambda v: torch.tensor(v, dtype=torch.float32)
+    a, b, lp = t["q1"], t["q2"], t["logp"]
+    el = f(alpha) * lp - torch.min(a, b)
+    tie = a == b
+    g1 = torch.where(tie, f(-0.5), torch.where(a < b, f(-1.0), f(0.0))) \
+        / float(B)
+    g2 = torch.where(tie, f(-0.5), torch.where(b < a, f(-1.0), f(0.0))) \
+        / float(B)
+    return dict(loss=el.sum() / float(B), mean_logp=lp.sum() / float(B),
+                dq1=g1, dq2=g2, dy0=g1[:, None] * t["wt0"][None],
+                dy1=g2[:, None] * t["wt1"][None])
+
+
+# ---- alpha_update -------------------------------------------------------------
+
+ALPHA_LR = 3e-4
+ALPHA_TARGET_ENTROPY = -6.0
+# one fresh mean_logp per step; step 3 has mean_logp == -target_entropy
+# exactly in fp32, so its gradient is 0
+ALPHA_MEAN_LOGP = [-3.7251, 9.13, 6.0, -0.00317, 2.5e3]
+ALPHA_LOG0 = math.log(0.2)
+
+
+def alpha_ref(log_alpha, m, v, step, mean_logp, target_entropy, lr):
+    """One float64 step of alpha_update_kernel from the fp32 state
+    (log_alpha, m, v) and the step count BEFORE the call.  The kernel's
+    literals enter as fp32 constants: 0.001f is not 1 - 0.999f (they differ
+    by 1.3e-5 relative), so adam_ref cannot stand in for v.  Returns
+    (log_alpha, m, v, u, g): the new state, the update term and the
+    gradient."""
+    c = {k: f32_as_double(x) for k, x in
+         dict(b1=0.9, a1=0.1, b2=0.999, a2=0.001, eps=1e-8).items()}
+    la, m, v, ml, te, lr = (f32_as_double(x) for x in
+                            (log_alpha, m, v, mean_logp, target_entropy, lr))
+    g = -(ml + te)
+    t = float(step + 1)
+    mi = c["b1"] * m + c["a1"] * g
+    vi = c["b2"] * v + c["a2"] * g * g
+    bc1 = 1.0 - c["b1"] ** t
+    bc2 = 1.0 - c["b2"] ** t
+    u = lr / bc1 * mi / (math.sqrt(vi / bc2) + c["eps"])
+    return la - u, mi, vi, u, g
+
+
+def alpha_bounds(m, v, ref):
+    """Bounds (log_alpha, m, v) on |kernel - alpha_ref| for one step.  g is
+    one rounded sum; m and v are three rounded operations each on top of
+    it; log_alpha is one final rounding plus the update's relative error,
+    dominated by the cancellation in 1 - powf(b, t) (the 1e-4 |u| term
+    kernel_refs.adam_bounds justifies)."""
+    la, mi, vi, u, g = ref
+    m, v = f32_as_double(m), f32_as_double(v)
+    b_g = U * abs(g)
+    b_m = 0.1 * b_g + U * (0.9 * abs(m) + 0.1 * abs(g)) + U * abs(mi)
+    b_v = 0.001 * 2 * abs(g) * b_g \
+        + U * (0.999 * v + 2 * 0.001 * g * g) + U * vi
+    # the errors of m and v reach u through du/dm = u / m and
+    # |du/dv| <= |u| / (2 v)
+    b_u = 1e-4 * abs(u)
+    if mi != 0.0:
+        b_u += abs(u / mi) * b_m + abs(u) / (2 * vi) * b_v
+    b_la = float(ulp32(torch.tensor(la, dtype=torch.float64))) + b_u
+    return b_la, b_m + 1e-45, b_v + 1e-45
+
+
+def alpha_f32(log_alpha, m, v, step, mean_logp, target_entropy, lr):
+    """Plain fp32 step in alpha_update_kernel's order: (log_alpha, m, v)."""
+    f = lambda x: torch.tensor(x, dtype=torch.float32)
+    g = -(f(mean_logp) + f(target_entropy))
+    t = f(float(step + 1))
+    mi = f(0.9) * f(m) + f(0.1) * g
+    vi = f(0.999) * f(v) + f(0.001) * g * g
+    bc1 = 1.0 - torch.pow(f(0.9), t)
+    bc2 = 1.0 - torch.pow(f(0.999), t)
+    la = f(log_alpha) - f(lr) / bc1 * mi / (torch.sqrt(vi / bc2) + f(1e-8))
+    return float(la), float(mi), float(vi)

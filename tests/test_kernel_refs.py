@@ -6,8 +6,12 @@ sum|a||b| stay below 2^24.  Then every partial sum any kernel can form,
 in fp32 or from bf16-rounded operands, is exact, and bit equality is the
 right assertion.  Also asserts the launch plans the wgrad case tables are
 listed with, and that a plain fp32 evaluation of Adam stays within half
-of the bounds the GPU Adam tests assert (test_gpu_adam_t.py)."""
+of the bounds the GPU Adam tests assert (test_gpu_adam_t.py).  The host
+Philox4x32-10 is held to the published known-answer vectors, and the
+bounds of test_gpu_heads_losses.py and the noise cap of test_gpu_philox.py
+to the same fairness condition as Adam's."""
 
+import numpy as np
 import pytest
 import torch
 
@@ -358,3 +362,231 @@ def test_conv_geometry_table_properties():
     # ragged wgrad slab plan: M = 126 -> 64 + 62
     assert any(g[0] * kr.conv_out_hw(g)[0] * kr.conv_out_hw(g)[1] == 126
                for g in kr.CONV_GEOMS)
+
+
+# ---------------------------------------------------------------------------
+# Philox4x32-10 and the draws derived from it
+# ---------------------------------------------------------------------------
+
+# (counter c0..c3, key k0 k1, output): the known-answer vectors published
+# with the generator (Random123, kat_vectors, philox4x32 10 rounds)
+PHILOX_KAT = [
+    ((0, 0, 0, 0), (0, 0),
+     (0x6627e8d5, 0xe169c58d, 0xbc57ac4c, 0x9b00dbd8)),
+    ((0xffffffff,) * 4, (0xffffffff,) * 2,
+     (0x408f276d, 0x41c83b0e, 0xa20bc7c6, 0x6d5451fd)),
+    ((0x243f6a88, 0x85a308d3, 0x13198a2e, 0x03707344),
+     (0xa4093822, 0x299f31d0),
+     (0xd16cfe09, 0x94fdcceb, 0x5001e420, 0x24126ea1)),
+]
+
+
+@pytest.mark.parametrize("ctr,key,want", PHILOX_KAT)
+def test_philox_known_answers(ctr, key, want):
+    clo, chi = ctr[0] | (ctr[1] << 32), ctr[2] | (ctr[3] << 32)
+    seed = key[0] | (key[1] << 32)
+    assert kr.philox4x32(seed, chi, clo) == want
+    got = kr.philox4x32_np(seed, chi, np.array([clo], dtype=np.uint64))
+    assert got.dtype == np.uint32 and tuple(int(x) for x in got[0]) == want
+    # the signed form an int64 argument carries is the same key
+    assert kr.philox4x32(kr.as_i64(seed), kr.as_i64(chi), clo) == want
+    # nine rounds is another function
+    assert kr.philox4x32(seed, chi, clo, rounds=9) != want
+
+
+def test_philox_vectorised_matches_scalar():
+    """Across the 32-bit boundary of the subsequence index, with high
+    counter and key words set."""
+    seed, chi, clo0 = 0x9e3779b97f4a7c15, 2 ** 40 + 3, 2 ** 32 - 3
+    rows = kr.philox_rows(seed, chi, 7, clo0)
+    for i in range(7):
+        assert tuple(int(x) for x in rows[i]) == \
+            kr.philox4x32(seed, chi, clo0 + i)
+    assert len({tuple(r) for r in rows.tolist()}) == 7
+
+
+def test_uniform32_edges():
+    u = kr.uniform32(np.array([0, 0xffffffff, 0x7fffffff], dtype=np.uint32))
+    assert u.dtype == np.float32
+    assert float(u[0]) == 2.0 ** -32
+    assert float(u[1]) == 1.0            # 2^32 - 1 rounds to 2^32; never > 1
+    assert float(u[2]) == 0.5
+    c, s, r = kr.box_muller64(u[1:2], u[0:1])
+    assert float(r[0]) == 0.0 and float(c[0]) == 0.0 and float(s[0]) == 0.0
+
+
+def test_draw_index_and_shifts():
+    x, y = 0xdeadbeef, 0x01234567
+    u = (x << 32) | y
+    big = 2 ** 32 + 12345                # a ring larger than one word
+    assert kr.draw_index(x, y, big) == u % big
+    assert kr.draw_index(x, y, big) != kr.draw_index(0, y, big)
+    assert kr.draw_index(x, y, 1) == 0
+    xs = np.array([x, 0, 0xffffffff], dtype=np.uint32)
+    ys = np.array([y, 5, 0xffffffff], dtype=np.uint32)
+    for size in (1, 48, 5000, big):
+        got = kr.draw_index(xs, ys, size)
+        assert got.dtype == np.int64
+        assert got.tolist() == [((int(a) << 32) | int(b)) % size
+                                for a, b in zip(xs, ys)]
+    z, w = 0x00070003, 0xfffe0009
+    assert kr.draw_shifts(z, w, 0).tolist() == [0, 0, 0, 0]
+    assert kr.draw_shifts(z, w, 1).tolist() == \
+        [7 % 3 - 1, 3 % 3 - 1, 0xfffe % 3 - 1, 9 % 3 - 1]
+    assert kr.draw_shifts(z, w, 4).tolist() == \
+        [7 - 4, 3 - 4, 0xfffe % 9 - 4, 0 - 4]
+    both = kr.draw_shifts(np.array([z, w]), np.array([w, z]), 4)
+    assert both.shape == (2, 4) and both[1].tolist() == \
+        [0xfffe % 9 - 4, -4, 3, -1]
+
+
+def test_per_targets_formula():
+    x = np.array([0, 0xffffffff, 0x80000000], dtype=np.uint32)
+    u = kr.per_targets(x, 6.0, 3)
+    assert u.dtype == np.float32
+    assert u.tolist() == [0.0, float(np.float32(2 - 2.0 ** -24) * 2), 5.0]
+
+
+def test_box_muller_cap_is_fair():
+    """numpy's fp32 evaluation of the kernels' formula stays inside a
+    tenth of NOISE_CAP * max(1, R) against float64, on the draws the GPU
+    tests use and on the edge uniforms."""
+    words = [kr.philox_rows(s, c, 4096) for s, c in ((0, 1), (11, 41),
+                                                     (12345, 2 ** 33))]
+    w = np.concatenate(words)
+    edge = np.array([0, 1, 2, 0x7fffffff, 0x80000000, 0xfffffeff,
+                     0xffffff00, 0xffffffff], dtype=np.uint32)
+    u0 = np.concatenate([kr.uniform32(w[:, 0]), kr.uniform32(w[:, 2]),
+                         np.repeat(kr.uniform32(edge), len(edge))])
+    u1 = np.concatenate([kr.uniform32(w[:, 1]), kr.uniform32(w[:, 3]),
+                         np.tile(kr.uniform32(edge), len(edge))])
+    c64, s64, r = kr.box_muller64(u0, u1)
+    c32, s32 = kr.box_muller32(u0, u1)
+    cap = kr.NOISE_CAP * np.maximum(1.0, r)
+    worst = max(float((np.abs(c32 - c64) / cap).max()),
+                float((np.abs(s32 - s64) / cap).max()))
+    print("fp32 Box-Muller worst err / cap:", worst)
+    assert worst <= 0.1
+    # a structural error is O(1): sin for cos, swapped uniforms
+    assert float(np.abs(s64 - c64).mean()) > 0.5
+    c_sw, _, _ = kr.box_muller64(u1, u0)
+    assert float(np.abs(c_sw - c64).mean()) > 0.5
+
+
+# ---------------------------------------------------------------------------
+# head / loss / temperature bounds are fair to a correct fp32 evaluation
+# ---------------------------------------------------------------------------
+
+def _worst(name, out, ref, bound):
+    ratio = float(((out.double() - ref).abs() / bound).max())
+    print(f"{name}: fp32 emulation max err/bound = {ratio:.3f}")
+    return ratio
+
+
+@pytest.mark.parametrize("case", kr.TG_CASES, ids=kr.tg_id)
+def test_tg_bounds_are_fair(case):
+    R, A = case[:2]
+    hl = kr.tg_hl(case)
+    eps = kr.noise_eps32(kr.TG_SEED, kr.TG_CTR, R, A)
+    args = (kr.TG_ACT_LIMIT, kr.TG_LO, kr.TG_HI)
+    ref = kr.tg_ref(hl, eps, *args)
+    bnd = kr.tg_fwd_bounds(hl, eps, *args)
+    out = kr.tg_fwd_f32(hl, eps, *args)
+    for nm, o, r, b in zip(("pi", "prob", "logp"), out, ref, bnd):
+        assert _worst(f"tg_fwd {kr.tg_id(case)} {nm}", o, r, b) <= 0.5, nm
+    B = kr.tg_bwd_rows(case)
+    dxa, dxb, col = kr.tg_bwd_operands(case, B)
+    da, db = dxa[:, col:col + A], dxb[:, col:col + A]
+    prob = out[1]
+    for second in (db, None):
+        a = (hl, prob, da, second, 0.2, B) + args
+        ref_b, bnd_b = kr.tg_bwd_ref(*a), kr.tg_bwd_bounds(*a)
+        out_b = kr.tg_bwd_f32(*a)
+        for nm, o, r, b in zip(("dmu", "dls"), out_b, ref_b, bnd_b):
+            assert _worst(f"tg_bwd {kr.tg_id(case)} {nm}", o, r, b) <= 0.5
+        # the clamp mask: zero strictly outside, alive at both ends
+        raw = hl[:B, A:]
+        outside = (raw < kr.TG_LO) | (raw > kr.TG_HI)
+        assert bool((ref_b[1][outside] == 0).all())
+        assert bool((ref_b[1][~outside] != 0).all())
+
+
+def test_tg_inputs_reach_every_branch():
+    """Between them the cases hold every special log_std next to every
+    special mu, x = -2 prob above 20 (the softplus cut) and saturated
+    tanh."""
+    seen_ls, seen_mu, cut, sat = set(), set(), 0, 0
+    for case in kr.TG_CASES:
+        R, A = case[:2]
+        hl = kr.tg_hl(case)
+        seen_mu |= set(hl[:, :A].reshape(-1).tolist())
+        seen_ls |= set(hl[:, A:].reshape(-1).tolist())
+        eps = kr.noise_eps32(kr.TG_SEED, kr.TG_CTR, R, A)
+        _, prob, _ = kr.tg_ref(hl, eps, kr.TG_ACT_LIMIT, kr.TG_LO, kr.TG_HI)
+        cut += int((-2 * prob > 20).sum())
+        sat += int((prob.abs() > 10).sum())
+        assert case[4] + A <= case[3] and case[6] + A <= case[5]
+        assert 0 <= case[2] <= R
+    assert set(kr.TG_MU) <= seen_mu
+    assert set(torch.tensor(kr.tg_raw_log_std()).tolist()) <= seen_ls
+    assert cut >= 10 and sat >= 20
+    big = kr.tg_hl(kr.TG_CASES[-1])
+    A = kr.TG_CASES[-1][1]
+    pairs = {(m, s) for m, s in zip(big[:, :A].reshape(-1).tolist(),
+                                    big[:, A:].reshape(-1).tolist())}
+    want = {(m, s) for m in kr.TG_MU
+            for s in torch.tensor(kr.tg_raw_log_std()).tolist()}
+    assert want <= pairs
+
+
+@pytest.mark.parametrize("B", kr.LOSS_B_FUSED + [kr.LOSS_B_UNFUSED])
+def test_loss_bounds_are_fair(B):
+    h = kr.QLOSS_HYPER
+    for h2 in kr.LOSS_H2:
+        t = kr.qloss_inputs(B, h2)
+        assert B == 1 or set(t["done"].tolist()) == {0.0, 1.0}
+        ref, bnd = kr.qloss_ref(t, B, h["alpha"], h["gamma"], h["scale"])
+        out = kr.qloss_f32(t, B, h["alpha"], h["gamma"], h["scale"])
+        for k in ref:
+            assert _worst(f"qloss B={B} h2={h2} {k}", out[k], ref[k],
+                          bnd[k]) <= 0.5, k
+        t = kr.piloss_inputs(B, h2)
+        tie = t["q1"] == t["q2"]
+        assert int(tie.sum()) == -(-B // 3)
+        assert int((t["q1"] < t["q2"]).sum()) == -(-(B - 1) // 3)
+        ref, bnd = kr.piloss_ref(t, B, h["alpha"])
+        out = kr.piloss_f32(t, B, h["alpha"])
+        for k in ref:
+            if k.startswith("dq"):
+                assert torch.equal(out[k].double(),
+                                   ref[k].float().double()), k
+            else:
+                assert _worst(f"piloss B={B} h2={h2} {k}", out[k], ref[k],
+                              bnd[k] + 1e-300) <= 0.5, k
+        assert bool((ref["dq1"][tie] == -0.5 / B).all())
+        assert bool((ref["dq2"][tie] == -0.5 / B).all())
+
+
+def test_alpha_bounds_are_fair():
+    """Five chained fp32 steps, each held against the float64 step from
+    the same fp32 state."""
+    assert kr.f32_as_double(0.001) != 1.0 - kr.f32_as_double(0.999)
+    assert abs(kr.f32_as_double(0.001) / (1.0 - kr.f32_as_double(0.999))
+               - 1.0) > 1e-5
+    la, m, v = float(torch.tensor(kr.ALPHA_LOG0)), 0.0, 0.0
+    zero_g = 0
+    for step, ml in enumerate(kr.ALPHA_MEAN_LOGP):
+        a = (la, m, v, step, ml, kr.ALPHA_TARGET_ENTROPY, kr.ALPHA_LR)
+        ref = kr.alpha_ref(*a)
+        bnd = kr.alpha_bounds(m, v, ref)
+        out = kr.alpha_f32(*a)
+        zero_g += ref[4] == 0.0
+        for nm, o, r, b in zip(("log_alpha", "m", "v"), out, ref, bnd):
+            ratio = abs(o - r) / b
+            print(f"alpha step {step + 1} {nm}: err/bound = {ratio:.3f}")
+            assert ratio <= 0.5, (step, nm)
+        if step > 0 and ref[4] != 0.0:
+            # the update is visible against its own bound
+            assert abs(ref[3]) > 100 * bnd[0]
+        la, m, v = out
+    assert zero_g == 1

@@ -65,6 +65,21 @@ DEVINL P4 philox_(uint64_t seed, uint64_t chi, uint64_t clo) {
   return {c0, c1, c2, c3};
 }
 
+// Debug/test helper: the four raw output words of subsequences
+// clo0 .. clo0 + n - 1, so the generator itself can be held against a
+// host implementation (tests/kernel_refs.py::philox4x32).
+__global__ __launch_bounds__(256)
+void philox_words2_kernel(int64_t* __restrict__ out, uint64_t seed,
+                          uint64_t chi, uint64_t clo0, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  P4 r = philox_(seed, chi, clo0 + (uint64_t)i);
+  out[4 * i + 0] = (int64_t)r.x;
+  out[4 * i + 1] = (int64_t)r.y;
+  out[4 * i + 2] = (int64_t)r.z;
+  out[4 * i + 3] = (int64_t)r.w;
+}
+
 // ---------------------------------------------------------------------------
 // Multi-problem MFMA GEMM (fwd-form): y = act(x @ w^T + b), x optionally
 // relu-masked by `mask` (backward chain), optional second (x2,w2,mask2)
@@ -3219,13 +3234,100 @@ void per_set_range(torch::Tensor tree, int64_t cap, int64_t start,
                      max_priority.data_ptr<float>());
 }
 
+// Host gates of the head / loss / temperature bindings below: every
+// operand is checked before the launch, so a refused call touches nothing.
+inline void need_f32(const torch::Tensor& t, int64_t n, const char* op,
+                     const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32 &&
+              t.is_contiguous() && t.numel() >= n, op, ": ", name,
+              " must be a contiguous fp32 device tensor of at least ", n,
+              " elements");
+}
+
+inline void need_f32_opt(const c10::optional<torch::Tensor>& t, int64_t n,
+                         const char* op, const char* name) {
+  if (t.has_value()) need_f32(*t, n, op, name);
+}
+
+inline void need_scalar_f32(const torch::Tensor& t, const char* op,
+                            const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32 &&
+              t.numel() == 1, op, ": ", name,
+              " must be an fp32 device tensor of one element");
+}
+
+inline void need_scalar_i64(const torch::Tensor& t, const char* op,
+                            const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kInt64 &&
+              t.numel() == 1, op, ": ", name,
+              " must be an int64 device tensor of one element");
+}
+
+// hl = [R, 2A] (mu | log_std), one 64-lane block per row; returns A
+inline int need_hl(const torch::Tensor& hl, int64_t min_rows, const char* op) {
+  TORCH_CHECK(hl.dim() == 2 && hl.size(0) >= 1 && hl.size(0) >= min_rows &&
+              hl.size(0) < (int64_t(1) << 31) && hl.size(1) >= 2 &&
+              hl.size(1) % 2 == 0, op, ": hl must be [R, 2A] with R >= ",
+              min_rows < 1 ? 1 : min_rows);
+  need_f32(hl, 0, op, "hl");
+  const int64_t A = hl.size(1) / 2;
+  TORCH_CHECK(A <= 64, op, ": A = ", A,
+              " exceeds the 64 lanes a row's block has");
+  return (int)A;
+}
+
+// A [rows, A] block of a 2-D slab starting `off` elements into it: off may
+// carry whole rows (the engine addresses rows B.. of XC that way); the
+// block must stay inside the slab's columns and rows.
+inline void need_slab(const torch::Tensor& t, int64_t off, int64_t rows,
+                      int64_t A, const char* op, const char* name) {
+  need_f32(t, 0, op, name);
+  TORCH_CHECK(t.dim() == 2 && t.size(1) >= 1, op, ": ", name,
+              " must be 2-D");
+  const int64_t ld = t.size(1);
+  TORCH_CHECK(off >= 0 && off % ld + A <= ld, op, ": columns [", off % ld,
+              ", ", off % ld + A, ") leave ", name, "'s ", ld, " columns");
+  TORCH_CHECK(off / ld + rows <= t.size(0), op, ": ", name, " has ",
+              t.size(0), " rows, ", off / ld + rows, " needed");
+}
+
+// fused K = 1 dgrad operands of the loss kernels: all four or none
+inline bool need_fuse(const c10::optional<torch::Tensor>& wt3_0,
+                      const c10::optional<torch::Tensor>& wt3_1,
+                      const c10::optional<torch::Tensor>& dy2_0,
+                      const c10::optional<torch::Tensor>& dy2_1,
+                      int64_t B, int64_t h2, const char* op) {
+  const bool fuse = dy2_0.has_value();
+  if (!fuse) {
+    TORCH_CHECK(!dy2_1.has_value(), op, ": dy2_1 given without dy2_0");
+    return false;
+  }
+  TORCH_CHECK(B <= LOSS_MAXB, op, ": the fused dgrad stages dq in LDS and "
+              "takes at most ", LOSS_MAXB, " rows, got ", B);
+  TORCH_CHECK(wt3_0.has_value() && wt3_1.has_value() && dy2_1.has_value() &&
+              h2 >= 1, op, ": the fused dgrad needs wt3_0, wt3_1, dy2_0, "
+              "dy2_1 and h2 >= 1");
+  need_f32(*wt3_0, h2, op, "wt3_0");
+  need_f32(*wt3_1, h2, op, "wt3_1");
+  need_f32(*dy2_0, B * h2, op, "dy2_0");
+  need_f32(*dy2_1, B * h2, op, "dy2_1");
+  return true;
+}
+
 void tg_fwd2(torch::Tensor hl, torch::Tensor out0,
              int64_t col0, torch::Tensor out1, int64_t col1, int64_t B0,
              torch::Tensor logp, torch::Tensor prob, torch::Tensor ctr,
              int64_t seed, double act_limit, double lo, double hi,
              int64_t ctr_add) {
-  const int R = (int)hl.size(0), A = (int)hl.size(1) / 2;
-  TORCH_CHECK(A <= 64);
+  const int A = need_hl(hl, 1, "tg_fwd2");
+  const int R = (int)hl.size(0);
+  TORCH_CHECK(B0 >= 0 && B0 <= R, "tg_fwd2: B0 = ", B0, " outside [0, R = ",
+              R, "]");
+  need_slab(out0, col0, B0, A, "tg_fwd2", "out0");
+  need_slab(out1, col1, R - B0, A, "tg_fwd2", "out1");
+  need_f32(logp, R, "tg_fwd2", "logp");
+  need_f32(prob, (int64_t)R * A, "tg_fwd2", "prob");
+  need_scalar_i64(ctr, "tg_fwd2", "ctr");
   hipLaunchKernelGGL(tg_fwd2_kernel, dim3(R), dim3(64), 0, stream(),
                      hl.data_ptr<float>(),
                      out0.data_ptr<float>() + col0, (int)out0.size(1),
@@ -3241,7 +3343,25 @@ void tg_bwd2(torch::Tensor dxc, int64_t col0,
              torch::Tensor hl, torch::Tensor prob,
              torch::Tensor dmu, torch::Tensor dls, int64_t B,
              double act_limit, double lo, double hi) {
-  const int A = (int)dmu.size(1);
+  TORCH_CHECK(B >= 1 && B < (int64_t(1) << 31), "tg_bwd2: B must be >= 1");
+  const int A = need_hl(hl, B, "tg_bwd2");
+  need_f32(dmu, 0, "tg_bwd2", "dmu");
+  need_f32(dls, 0, "tg_bwd2", "dls");
+  TORCH_CHECK(dmu.dim() == 2 && dmu.size(0) == B && dmu.size(1) == A &&
+              dls.dim() == 2 && dls.size(0) == B && dls.size(1) == A,
+              "tg_bwd2: dmu and dls must be [B, A] = [", B, ", ", A, "]");
+  need_f32(prob, B * A, "tg_bwd2", "prob");
+  TORCH_CHECK(col0 < (int64_t(1) << 31) &&
+              (dxc.dim() != 2 || col0 < dxc.size(1)),
+              "tg_bwd2: col0 is a column of dxc");
+  need_slab(dxc, col0, B, A, "tg_bwd2", "dxc");
+  if (dxc2.has_value()) {
+    need_f32(*dxc2, 0, "tg_bwd2", "dxc2");
+    TORCH_CHECK(dxc2->sizes() == dxc.sizes(),
+                "tg_bwd2: dxc2 must have dxc's shape");
+  }
+  if (alpha_dev.has_value())
+    need_scalar_f32(*alpha_dev, "tg_bwd2", "alpha_dev");
   hipLaunchKernelGGL(tg_bwd2_kernel, dim3((int)B), dim3(64), 0, stream(),
                      dxc.data_ptr<float>(), (int)dxc.size(1), (int)col0,
                      fptr(dxc2),
@@ -3268,8 +3388,23 @@ void qloss2(torch::Tensor q1, torch::Tensor q2, torch::Tensor q1t,
             c10::optional<torch::Tensor> size_dev,
             c10::optional<torch::Tensor> beta_dev,
             c10::optional<torch::Tensor> td) {
-  const bool fuse = dy2_0.has_value();
-  TORCH_CHECK(!fuse || B <= LOSS_MAXB);
+  TORCH_CHECK(B >= 1 && B < (int64_t(1) << 31), "qloss2: B must be >= 1");
+  const bool fuse = need_fuse(wt3_0, wt3_1, dy2_0, dy2_1, B, h2, "qloss2");
+  need_f32(q1, B, "qloss2", "q1");
+  need_f32(q2, B, "qloss2", "q2");
+  need_f32(q1t, B, "qloss2", "q1t");
+  need_f32(q2t, B, "qloss2", "q2t");
+  need_f32(logp_next, B, "qloss2", "logp_next");
+  need_f32(rew, B, "qloss2", "rew");
+  need_f32(done, B, "qloss2", "done");
+  need_f32(dq1, B, "qloss2", "dq1");
+  need_f32(dq2, B, "qloss2", "dq2");
+  need_scalar_f32(loss_acc, "qloss2", "loss_acc");
+  if (alpha_dev.has_value())
+    need_scalar_f32(*alpha_dev, "qloss2", "alpha_dev");
+  if (bump0.has_value()) need_scalar_i64(*bump0, "qloss2", "bump0");
+  if (bump1.has_value()) need_scalar_i64(*bump1, "qloss2", "bump1");
+  if (bump2.has_value()) need_scalar_i64(*bump2, "qloss2", "bump2");
   auto iptr = [](const c10::optional<torch::Tensor>& t) -> int64_t* {
     return t.has_value() ? t->data_ptr<int64_t>() : nullptr;
   };
@@ -3296,7 +3431,8 @@ void qloss2(torch::Tensor q1, torch::Tensor q2, torch::Tensor q1t,
                      (float)alpha_host, loss_acc.data_ptr<float>(),
                      dq1.data_ptr<float>(), dq2.data_ptr<float>(), (int)B,
                      (float)gamma, (float)scale,
-                     fptr(wt3_0), fptr(wt3_1),
+                     fuse ? fptr(wt3_0) : nullptr,
+                     fuse ? fptr(wt3_1) : nullptr,
                      fuse ? dy2_0->data_ptr<float>() : nullptr,
                      fuse ? dy2_1->data_ptr<float>() : nullptr, (int)h2,
                      iptr(bump0), iptr(bump1), iptr(bump2), fptr(prob),
@@ -3313,8 +3449,18 @@ void piloss2(torch::Tensor q1, torch::Tensor q2, torch::Tensor logp,
              c10::optional<torch::Tensor> wt3_1,
              c10::optional<torch::Tensor> dy2_0,
              c10::optional<torch::Tensor> dy2_1, int64_t h2) {
-  const bool fuse = dy2_0.has_value();
-  TORCH_CHECK(!fuse || B <= LOSS_MAXB);
+  TORCH_CHECK(B >= 1 && B < (int64_t(1) << 31), "piloss2: B must be >= 1");
+  const bool fuse = need_fuse(wt3_0, wt3_1, dy2_0, dy2_1, B, h2, "piloss2");
+  need_f32(q1, B, "piloss2", "q1");
+  need_f32(q2, B, "piloss2", "q2");
+  need_f32(logp, B, "piloss2", "logp");
+  need_f32(dq1, B, "piloss2", "dq1");
+  need_f32(dq2, B, "piloss2", "dq2");
+  need_scalar_f32(loss_acc, "piloss2", "loss_acc");
+  if (alpha_dev.has_value())
+    need_scalar_f32(*alpha_dev, "piloss2", "alpha_dev");
+  if (mean_logp.has_value())
+    need_scalar_f32(*mean_logp, "piloss2", "mean_logp");
   hipLaunchKernelGGL(piloss2_kernel, dim3(1), dim3(256), 0, stream(),
                      q1.data_ptr<float>(), q2.data_ptr<float>(),
                      logp.data_ptr<float>(), fptr(alpha_dev),
@@ -3380,6 +3526,11 @@ void adam_t(torch::Tensor p, torch::Tensor g, torch::Tensor m,
 
 torch::Tensor tg_eps(int64_t ctr_val, int64_t seed, int64_t R, int64_t A,
                      torch::Tensor like) {
+  TORCH_CHECK(A >= 1 && A <= 64, "tg_eps: A = ", A,
+              " outside 1..64 (one 64-lane block per row)");
+  TORCH_CHECK(R >= 1 && R < (int64_t(1) << 31), "tg_eps: R must be >= 1");
+  TORCH_CHECK(like.is_cuda() && like.scalar_type() == torch::kFloat32,
+              "tg_eps: `like` must be an fp32 device tensor");
   auto out = torch::empty({R, A}, like.options());
   hipLaunchKernelGGL(tg_eps_kernel, dim3((int)R), dim3(64), 0, stream(),
                      out.data_ptr<float>(), (uint64_t)ctr_val,
@@ -3584,9 +3735,27 @@ void act_batch(torch::Tensor x, std::vector<torch::Tensor> ws,
                      (unsigned long long)ctr_val);
 }
 
+torch::Tensor philox_words2(int64_t seed, int64_t chi, int64_t clo0,
+                            int64_t n) {
+  TORCH_CHECK(n >= 1 && n <= (int64_t(1) << 20),
+              "philox_words2: n outside 1..2^20");
+  auto out = torch::empty({n, 4}, torch::dtype(torch::kInt64)
+                                      .device(torch::kCUDA));
+  hipLaunchKernelGGL(philox_words2_kernel, dim3((int)((n + 255) / 256)),
+                     dim3(256), 0, stream(), out.data_ptr<int64_t>(),
+                     (uint64_t)seed, (uint64_t)chi, (uint64_t)clo0, n);
+  return out;
+}
+
 void alpha_update(torch::Tensor log_alpha, torch::Tensor alpha_dev,
                   torch::Tensor m, torch::Tensor v, torch::Tensor step,
                   torch::Tensor mean_logp, double target_entropy, double lr) {
+  need_scalar_f32(log_alpha, "alpha_update", "log_alpha");
+  need_scalar_f32(alpha_dev, "alpha_update", "alpha_dev");
+  need_scalar_f32(m, "alpha_update", "m");
+  need_scalar_f32(v, "alpha_update", "v");
+  need_scalar_i64(step, "alpha_update", "step");
+  need_scalar_f32(mean_logp, "alpha_update", "mean_logp");
   hipLaunchKernelGGL(alpha_update_kernel, dim3(1), dim3(1), 0, stream(),
                      log_alpha.data_ptr<float>(), alpha_dev.data_ptr<float>(),
                      m.data_ptr<float>(), v.data_ptr<float>(),
@@ -3660,6 +3829,8 @@ void register_fused(pybind11::module_& m) {
   m.def("piloss2", &fused::piloss2);
   m.def("alpha_update", &fused::alpha_update);
   m.def("tg_eps", &fused::tg_eps);
+  m.def("philox_words2", &fused::philox_words2,
+        "test helper: raw Philox words of this translation unit's copy");
   m.def("adam_t", &fused::adam_t,
         pybind11::arg("p"), pybind11::arg("g"), pybind11::arg("m"),
         pybind11::arg("v"), pybind11::arg("step"), pybind11::arg("lr"),

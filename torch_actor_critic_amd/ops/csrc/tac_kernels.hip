@@ -68,6 +68,21 @@ DEVINL Philox4 philox4(uint64_t seed, uint64_t ctr_hi, uint64_t ctr_lo) {
   return {c0, c1, c2, c3};
 }
 
+// Debug/test helper: the four raw output words of subsequences
+// clo0 .. clo0 + n - 1, so the generator itself can be held against a
+// host implementation (tests/kernel_refs.py::philox4x32).
+__global__ __launch_bounds__(256)
+void philox_words_kernel(int64_t* __restrict__ out, uint64_t seed,
+                         uint64_t chi, uint64_t clo0, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Philox4 r = philox4(seed, chi, clo0 + (uint64_t)i);
+  out[4 * i + 0] = (int64_t)r.x;
+  out[4 * i + 1] = (int64_t)r.y;
+  out[4 * i + 2] = (int64_t)r.z;
+  out[4 * i + 3] = (int64_t)r.w;
+}
+
 // ---------------------------------------------------------------------------
 // Counter bump (predecessor kernel for graph-safe RNG / Adam step)
 // ---------------------------------------------------------------------------
@@ -2099,6 +2114,18 @@ void bump_counter(torch::Tensor ctr) {
                      ctr.data_ptr<int64_t>());
 }
 
+torch::Tensor philox_words(int64_t seed, int64_t chi, int64_t clo0,
+                           int64_t n) {
+  TORCH_CHECK(n >= 1 && n <= (int64_t(1) << 20),
+              "philox_words: n outside 1..2^20");
+  auto out = torch::empty({n, 4}, torch::dtype(torch::kInt64)
+                                      .device(torch::kCUDA));
+  hipLaunchKernelGGL(philox_words_kernel, dim3((int)((n + 255) / 256)),
+                     dim3(256), 0, cur_stream(), out.data_ptr<int64_t>(),
+                     (uint64_t)seed, (uint64_t)chi, (uint64_t)clo0, n);
+  return out;
+}
+
 void philox_randn_(torch::Tensor out, torch::Tensor ctr, int64_t seed) {
   CHECK_IN(out);
   int64_t n = out.numel();
@@ -2208,5 +2235,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("visual_store_into_n", &visual_store_into_n,
         "visual_store_into plus episode_end and the write-head mirror");
   m.def("philox_randn_", &philox_randn_);
+  m.def("philox_words", &philox_words,
+        "test helper: raw Philox words of this translation unit's copy");
   m.def("bump_counter", &bump_counter);
 }
