@@ -1,7 +1,8 @@
 """Float64 CPU references, operand generators and case tables shared by
 test_gpu_mgemm.py, test_gpu_conv_exact.py, conv_lds_worker.py,
 test_gpu_wgrad.py, wgrad_env_worker.py, test_gpu_adam_t.py,
-test_gpu_philox.py, test_gpu_heads_losses.py and the CPU precondition test
+test_gpu_philox.py, test_gpu_heads_losses.py, test_gpu_autograd_kernels.py,
+test_gpu_dense_autograd.py and the CPU precondition test
 (test_kernel_refs.py).  Plain helper module, not a conftest.
 
 Two operand kinds:
@@ -1078,18 +1079,23 @@ def tg_bwd_rows(case):
     return case[2] if case[2] > 0 else case[0]
 
 
-def tg_bwd_ref(hl, prob, dpi_a, dpi_b, alpha, B, act_limit, lo, hi):
+def tg_bwd_ref(hl, prob, dpi_a, dpi_b, alpha, B, act_limit, lo, hi,
+               dl=None, se=None):
     """float64 (dmu, dls) of tg_bwd2 over rows :B.  dpi_a / dpi_b are the
     logical [B, A] gradient blocks (dpi_b may be None), prob the fp32
-    pre-squash sample the forward stored, alpha / B the seed of logp."""
+    pre-squash sample the forward stored, alpha / B the seed of logp.
+    The autograd-path kernel (tgh_bwd_ref) passes its own float64 seed
+    dl [B, 1] and its own se = std * eps [B, A] instead."""
     A = hl.shape[1] // 2
     al, lo, hi, alpha = (f32_as_double(v) for v in (act_limit, lo, hi, alpha))
     mu, raw = hl[:B, :A].double(), hl[:B, A:].double()
     p = prob[:B].double()
     t = p.tanh()
-    se = p - mu
+    if se is None:
+        se = p - mu
     dpi = dpi_a.double() + (dpi_b.double() if dpi_b is not None else 0.0)
-    dl = alpha / B
+    if dl is None:
+        dl = alpha / B
     dp = dpi * al * (1 - t * t)
     g_mu = dp + dl * t
     g_ls = dp * se + dl * (se * t - 1.0)
@@ -1098,49 +1104,59 @@ def tg_bwd_ref(hl, prob, dpi_a, dpi_b, alpha, B, act_limit, lo, hi):
 
 
 def tg_bwd_bounds(hl, prob, dpi_a, dpi_b, alpha, B, act_limit, lo, hi,
-                  tol=LIBM_TOL):
+                  tol=LIBM_TOL, dl=None, se=None, b_se=None):
     """Elementwise bounds (dmu, dls).  dp = dpi * act_limit * (1 - t^2)
     cancels to zero at saturation, so its error is carried as an absolute
-    one: t's error times 2|t|, plus the roundings of t^2 and of 1 - t^2."""
+    one: t's error times 2|t|, plus the roundings of t^2 and of 1 - t^2.
+    A seed dl given by the caller is an input (no error of its own) and
+    enters by its magnitude; se then comes with its own bound b_se."""
     A = hl.shape[1] // 2
     al, alpha = f32_as_double(act_limit), f32_as_double(alpha)
     mu = hl[:B, :A].double()
     p = prob[:B].double()
     t = p.tanh()
     b_t = tol["tanh"] * t.abs()
-    se = p - mu
-    b_se = U * se.abs()
+    if se is None:
+        se = p - mu
+        b_se = U * se.abs()
     dpi = dpi_a.double() + (dpi_b.double() if dpi_b is not None else 0.0)
     b_dpi = U * dpi.abs() if dpi_b is not None else torch.zeros_like(dpi)
-    dl = alpha / B
-    b_dl = U * dl
+    if dl is None:
+        dl = dl_s = alpha / B
+        b_dl = U * dl
+    else:
+        dl_s, dl, b_dl = dl, dl.abs(), 0.0
     om = 1 - t * t
     b_om = 2 * t.abs() * b_t + U * t * t + U * om
     dp = dpi * al * om
     b_dp = (dpi * al).abs() * b_om + al * om * b_dpi + U * dp.abs()
-    g_mu = dp + dl * t
+    g_mu = dp + dl_s * t
     b_mu = b_dp + t.abs() * b_dl + dl * b_t + U * (dl * t).abs() \
         + U * g_mu.abs()
     inner = se * t - 1.0
     b_in = t.abs() * b_se + se.abs() * b_t + U * (se * t).abs() \
         + U * inner.abs()
-    g_ls = dp * se + dl * inner
+    g_ls = dp * se + dl_s * inner
     b_ls = se.abs() * b_dp + dp.abs() * b_se + U * (dp * se).abs() \
         + dl * b_in + inner.abs() * b_dl + U * (dl * inner).abs() \
         + U * g_ls.abs()
     return b_mu + 1e-37, b_ls + 1e-37
 
 
-def tg_bwd_f32(hl, prob, dpi_a, dpi_b, alpha, B, act_limit, lo, hi):
-    """Plain fp32 (dmu, dls) in tg_bwd2_kernel's order."""
+def tg_bwd_f32(hl, prob, dpi_a, dpi_b, alpha, B, act_limit, lo, hi,
+               dl=None, se=None):
+    """Plain fp32 (dmu, dls) in tg_bwd2_kernel's order (dl and se as in
+    tg_bwd_ref, here in fp32)."""
     A = hl.shape[1] // 2
     f = lambda v: torch.tensor(v, dtype=torch.float32)
     mu, raw = hl[:B, :A], hl[:B, A:]
     p = prob[:B]
     t = p.tanh()
-    se = p - mu
+    if se is None:
+        se = p - mu
     dpi = dpi_a + dpi_b if dpi_b is not None else dpi_a
-    dl = f(alpha) / f(float(B))
+    if dl is None:
+        dl = f(alpha) / f(float(B))
     dp = dpi * f(act_limit) * (1.0 - t * t)
     g_mu = dp + dl * t
     g_ls = dp * se + dl * (se * t - 1.0)
@@ -1183,6 +1199,10 @@ def qloss_ref(t, B, alpha, gamma, scale):
     backup = t1 + t4
     b_t3 = U * (t2.abs() + t3.abs())
     b_t4 = U * t4.abs() + gd * b_t3 + U * gd * t3.abs()
+    # 1 - done is exact for done in {0, 1}; a fractional done (n-step
+    # sampling) costs one more rounding of the factor gd
+    frac = (d["done"] != 0.0) & (d["done"] != 1.0)
+    b_t4 = b_t4 + U * gd * t3.abs() * frac
     b_bk = U * (t1.abs() + backup.abs()) + b_t4
     ref, bnd = {}, {}
     s = torch.zeros(B, dtype=torch.float64)
@@ -1337,3 +1357,247 @@ def alpha_f32(log_alpha, m, v, step, mean_logp, target_entropy, lr):
     bc2 = 1.0 - torch.pow(f(0.999), t)
     la = f(log_alpha) - f(lr) / bc1 * mi / (torch.sqrt(vi / bc2) + f(1e-8))
     return float(la), float(mi), float(vi)
+
+
+# ---------------------------------------------------------------------------
+# The autograd-path kernels (tac_kernels.hip: tanh_gauss_fwd / _bwd,
+# sac_q_loss_fwd, sac_pi_loss_fwd, polyak_, adam_step_) and the eager
+# fallbacks of ops/functional.py
+# ---------------------------------------------------------------------------
+#
+# The head takes mu, log_std and eps as three [B, A] tensors; packed as
+# hl = mu | log_std it is the head of tg_ref, so tg_ref / tg_fwd_bounds /
+# tg_bwd_ref / tg_bwd_bounds serve it unchanged.  Deterministic means
+# eps = 0 there: prob = mu and the Gaussian term is -ls - log(2 pi) / 2.
+
+TGH_CASES = [(2, 1), (6, 6), (5, 17), (4, 64), (130, 33)]     # (B, A)
+TGH_CLAMPS = [(TG_LO, TG_HI), (-20.0, 2.0)]    # kernel_refs', the models'
+TGH_SMALL_LS = -16.0      # at and below this exp(ls) |eps| < ulp(0.5) / 2
+
+
+def tgh_id(v):
+    return "x".join(str(int(x)) for x in v)
+
+
+def tgh_raw_log_std(lo, hi):
+    """Raw log_std values every case cycles through: below, at and just
+    inside both clamp ends, an interior value, beyond the top; with a
+    bottom below TGH_SMALL_LS also -18 and -16, where std * eps drops
+    under the spacing of mu."""
+    inf = torch.tensor(float("inf"))
+    f = lambda v: torch.tensor(v, dtype=torch.float32)
+    out = [lo - 1.0, lo, float(torch.nextafter(f(lo), inf)), -1.25,
+           hi, float(torch.nextafter(f(hi), -inf)), hi + 3.0]
+    if lo < TGH_SMALL_LS:
+        out += [-18.0, TGH_SMALL_LS]
+    return out
+
+
+def tgh_inputs(B, A, lo, hi):
+    """fp32 (mu, log_std, eps) [B, A] in the pattern of tg_hl: all but two
+    of every len + 2 elements take the next special log_std, five of every
+    eight the next special mu (TG_MU: |mu| in {0, 0.5, 3, 12}; the periods
+    9 / 11 are coprime to 8, so all pairs occur in the large case).  eps is
+    a fixed seeded normal draw pushed out to |eps| >= 1 wherever the
+    clamped log_std is at most TGH_SMALL_LS."""
+    g = _gen(7500 + B * 100 + A + (1000 if lo < TGH_SMALL_LS else 0))
+    n = B * A
+    i = torch.arange(n) + B + A
+    mu = torch.randn(n, generator=g) * 2
+    ls = torch.rand(n, generator=g) * 5 - 4
+    eps = torch.randn(n, generator=g)
+    sp_mu = torch.tensor(TG_MU)
+    sp_ls = torch.tensor(tgh_raw_log_std(lo, hi))
+    ns = len(sp_ls)
+    km, kl = i % 8, i % (ns + 2)
+    mu = torch.where(km < 5, sp_mu[km.clamp_max(4)], mu)
+    ls = torch.where(kl < ns, sp_ls[kl.clamp_max(ns - 1)], ls)
+    small = ls.clamp(lo, hi) <= TGH_SMALL_LS
+    sign = torch.where(eps < 0, -1.0, 1.0)
+    eps = torch.where(small & (eps.abs() < 1), sign * (1 + eps.abs()), eps)
+    return (mu.view(B, A).contiguous(), ls.view(B, A).contiguous(),
+            eps.view(B, A).contiguous())
+
+
+def _tgh_pack(mu, log_std, eps, det):
+    hl = torch.cat([mu, log_std], 1)
+    return hl, (torch.zeros_like(eps) if det else eps)
+
+
+def tgh_ref(mu, log_std, eps, act_limit, lo, hi, det, with_logp):
+    """float64 (pi, prob, ls_c, logp) of tanh_gauss_fwd; logp is None
+    without the log-probability."""
+    hl, e = _tgh_pack(mu, log_std, eps, det)
+    pi, prob, logp = tg_ref(hl, e, act_limit, lo, hi)
+    ls_c = log_std.double().clamp(f32_as_double(lo), f32_as_double(hi))
+    return pi, prob, ls_c, (logp if with_logp else None)
+
+
+def tgh_fwd_bounds(mu, log_std, eps, act_limit, lo, hi, det, with_logp,
+                   tol=LIBM_TOL):
+    """Bounds (pi, prob, ls_c, logp) on |kernel - tgh_ref|.  ls_c is a
+    clamp and the deterministic prob a copy: both exact."""
+    hl, e = _tgh_pack(mu, log_std, eps, det)
+    b_pi, b_prob, b_logp = tg_fwd_bounds(hl, e, act_limit, lo, hi, tol=tol)
+    if det:
+        b_prob = torch.zeros_like(b_prob)
+    return b_pi, b_prob, torch.zeros_like(b_prob), \
+        (b_logp if with_logp else None)
+
+
+def tgh_fwd_f32(mu, log_std, eps, act_limit, lo, hi, det, with_logp):
+    """Plain fp32 (pi, prob, ls_c, logp) in tanh_gauss_fwd_kernel's order,
+    which is tg_fwd2_kernel's."""
+    hl, e = _tgh_pack(mu, log_std, eps, det)
+    pi, prob, logp = tg_fwd_f32(hl, e, act_limit, lo, hi)
+    f = lambda v: float(torch.tensor(v, dtype=torch.float32))
+    return pi, prob, log_std.clamp(f(lo), f(hi)), \
+        (logp if with_logp else None)
+
+
+def tgh_logp_by_subtraction_f32(mu, log_std, eps, lo, hi):
+    """fp32 logp as the head computed it before it took the noise from
+    eps: e = (prob - mu) / std rebuilt from prob = mu + std * eps.  Kept
+    to show on the CPU what tgh_inputs at the default clamp catch."""
+    f = lambda v: torch.tensor(v, dtype=torch.float32)
+    ls = log_std.clamp(float(f(lo)), float(f(hi)))
+    std = ls.exp()
+    prob = mu + std * eps
+    e = (prob - mu) / std
+    x = -2.0 * prob
+    sp = torch.where(x > 20.0, x, torch.log1p(torch.exp(x.clamp_max(20.0))))
+    gauss = -0.5 * e * e - ls - f(0.5) * f(1.8378770664093453)
+    corr = f(1.3862943611198906) - prob - sp
+    return (gauss - corr).sum(1)
+
+
+def tgh_bwd_operands(B, A):
+    """fp32 (dpi [B, A], dlogp [B]): general floats of both signs."""
+    g = _gen(7600 + B * 100 + A)
+    return torch.randn(B, A, generator=g), torch.randn(B, generator=g)
+
+
+def _tgh_bwd_terms(log_std, eps, ls_c, dlogp, det, with_logp):
+    """float64 seed dl [B, 1] and se = std * eps of the backward."""
+    e = torch.zeros_like(eps) if det else eps
+    se = ls_c.double().exp() * e.double()
+    dl = dlogp.double()[:, None] if with_logp \
+        else torch.zeros(len(dlogp), 1, dtype=torch.float64)
+    return dl, se
+
+
+def tgh_bwd_ref(mu, log_std, eps, prob, ls_c, dpi, dlogp, act_limit, lo, hi,
+                det, with_logp):
+    """float64 (dmu, dls) of tanh_gauss_bwd from the fp32 prob and ls_c
+    the forward stored: the gradient of
+        sum(dpi * pi) + sum(dlogp * logp)
+    with d prob / d log_std = std * eps (0 when deterministic), through
+    the clamp inclusively at both ends, as torch.clamp's backward."""
+    hl = torch.cat([mu, log_std], 1)
+    dl, se = _tgh_bwd_terms(log_std, eps, ls_c, dlogp, det, with_logp)
+    return tg_bwd_ref(hl, prob, dpi, None, 0.0, len(mu), act_limit, lo, hi,
+                      dl=dl, se=se)
+
+
+def tgh_bwd_bounds(mu, log_std, eps, prob, ls_c, dpi, dlogp, act_limit, lo,
+                   hi, det, with_logp, tol=LIBM_TOL):
+    """Bounds (dmu, dls): tg_bwd_bounds with se = exp(ls_c) * eps charged
+    one libm call and one rounding, and the seed an exact input."""
+    hl = torch.cat([mu, log_std], 1)
+    dl, se = _tgh_bwd_terms(log_std, eps, ls_c, dlogp, det, with_logp)
+    return tg_bwd_bounds(hl, prob, dpi, None, 0.0, len(mu), act_limit, lo,
+                         hi, tol=tol, dl=dl, se=se,
+                         b_se=(tol["exp"] + U) * se.abs())
+
+
+def tgh_bwd_f32(mu, log_std, eps, prob, ls_c, dpi, dlogp, act_limit, lo, hi,
+                det, with_logp):
+    """Plain fp32 (dmu, dls) in tanh_gauss_bwd_kernel's order."""
+    hl = torch.cat([mu, log_std], 1)
+    se = torch.zeros_like(eps) if det else ls_c.exp() * eps
+    dl = dlogp[:, None] if with_logp else torch.zeros(len(dlogp), 1)
+    return tg_bwd_f32(hl, prob, dpi, None, 0.0, len(mu), act_limit, lo, hi,
+                      dl=dl, se=se)
+
+
+# ---- sac_q_loss_fwd / sac_pi_loss_fwd ------------------------------------------
+#
+# qloss_ref / piloss_ref are the references (their dy0 / dy1 belong to the
+# fused kernels and are not used).  The kernels reduce per block, divide
+# each block's partial by B and add the quotients atomically in any order:
+# rounding_bound(B, .) holds for every order of the B + 63 additions, and
+# the divisions of the partials are within the U |loss| already charged.
+
+FLAT_LOSS_B = [1, 63, 64, 65, 255, 256, 257, 1000, 64 * 256 + 3]
+# done as an n-step buffer writes it: 1 - gamma^(M-1) (1 - done)
+FLAT_DONE_FRACTIONS = [1.0 - 0.99, 1.0 - 0.99 ** 2, 1.0 - 0.99 ** 4]
+
+
+def flat_qloss_inputs(B):
+    """qloss_inputs with fractional done on every fifth row and exact
+    q1t == q2t ties on every third."""
+    t = qloss_inputs(B, 1, seed=31)
+    i = torch.arange(B)
+    fr = torch.tensor(FLAT_DONE_FRACTIONS, dtype=torch.float32)
+    t["done"] = torch.where(i % 5 == 2, fr[(i // 5) % len(fr)], t["done"])
+    t["q2t"] = torch.where(i % 3 == 1, t["q1t"], t["q2t"])
+    return t
+
+
+def piloss_dlogp_ref(B, alpha):
+    """float64 seed of logp: the fp32 alpha over B, one correctly rounded
+    division in the kernel."""
+    return f32_as_double(alpha) / B
+
+
+# ---- polyak_ -----------------------------------------------------------------
+
+POLYAK_N = [1, 3, 4, 5, 1023, 1024 * 256 * 4 + 7]
+POLYAK_RHO = [0.995, 0.0, 1.0]
+
+
+def polyak_inputs(n, seed=0):
+    g = _gen(6500 + seed)
+    return torch.randn(n, generator=g), torch.randn(n, generator=g)
+
+
+def polyak_ref(targ, src, rho):
+    """float64 (new target, bound) of targ = rho targ + (1 - rho) src with
+    rho as the kernel holds it (fp32).  1 - rho is exact in fp32 for rho in
+    [0.5, 1] and for 0; three rounded operations remain (two products, one
+    sum), each charged U of its result.  A contraction into an FMA drops
+    one of them."""
+    r = f32_as_double(rho)
+    assert float(torch.tensor(1.0) - torch.tensor(rho, dtype=torch.float32)) \
+        == 1.0 - r
+    a = r * targ.double()
+    b = (1.0 - r) * src.double()
+    out = a + b
+    return out, U * (a.abs() + b.abs() + out.abs()) + 1e-45
+
+
+def polyak_f32(targ, src, rho):
+    """Plain fp32 evaluation in polyak_kernel's order."""
+    r = torch.tensor(rho, dtype=torch.float32)
+    return r * targ + (1.0 - r) * src
+
+
+# ---- adam_step_ ----------------------------------------------------------------
+
+ADAM_FLAT_N = [1, 255, 1024 * 256 + 777]
+ADAM_FLAT_STEPS = [1, 2, 1000, 100000]
+ADAM_FLAT_WD = [0.0, 2.0 ** -7]
+
+
+def adam_flat_f32(p, g, m, v, t, hyper):
+    """Plain fp32 (p, m, v) in adam_kernel's order (no FMA)."""
+    f = {k: torch.tensor(x, dtype=torch.float32) for k, x in hyper.items()}
+    one = torch.tensor(1.0)
+    tt = torch.tensor(float(t))
+    bc1 = one - torch.pow(f["b1"], tt)
+    bc2 = one - torch.pow(f["b2"], tt)
+    gi = g + f["wd"] * p
+    mi = f["b1"] * m + (one - f["b1"]) * gi
+    vi = f["b2"] * v + (one - f["b2"]) * gi * gi
+    pn = p - f["lr"] / bc1 * mi / (torch.sqrt(vi / bc2) + f["eps"])
+    return pn, mi, vi

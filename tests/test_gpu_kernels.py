@@ -122,8 +122,11 @@ def _ref_head(mu, log_std, eps, act_limit, lo, hi, det):
     std = torch.exp(ls)
     prob = mu if det else mu + std * eps
     pi = torch.tanh(prob) * act_limit
-    gauss = (-0.5 * ((prob - mu) / std) ** 2 - ls
-             - 0.5 * math.log(2 * math.pi)).sum(-1)
+    # the standardised residual (prob - mu) / std is eps itself (0 when
+    # deterministic); rebuilt by subtraction in fp32 it loses bits at a
+    # small std, up to 5e-4 of logp on these inputs (DEVIATIONS.md)
+    e = torch.zeros_like(eps) if det else eps
+    gauss = (-0.5 * e ** 2 - ls - 0.5 * math.log(2 * math.pi)).sum(-1)
     corr = (2 * math.log(2) - prob - F.softplus(-2 * prob)).sum(-1)
     return pi, gauss - corr
 

@@ -590,3 +590,235 @@ def test_alpha_bounds_are_fair():
             assert abs(ref[3]) > 100 * bnd[0]
         la, m, v = out
     assert zero_g == 1
+
+
+# ---------------------------------------------------------------------------
+# the autograd-path kernels: bounds are fair to a plain fp32 evaluation in
+# each kernel's order (half of every bound), and the eager fallbacks of
+# ops/functional.py meet the same references on the same inputs
+# ---------------------------------------------------------------------------
+
+TGH_VARIANTS = [(False, True), (False, False), (True, True), (True, False)]
+
+
+def _held(name, out, ref, bound, share=1.0):
+    bound = torch.as_tensor(bound, dtype=torch.float64) + 1e-300
+    r = _worst(name, out, ref, bound)
+    assert r <= share, (name, r)
+
+
+def _eager_head(mu, ls, eps, lo, hi, det, wl, dpi=None, dlogp=None):
+    """Fo's CPU head under autograd: (pi, logp, dmu, dls)."""
+    from torch_actor_critic_amd.ops import functional as Fo
+    mu = mu.clone().requires_grad_(True)
+    ls = ls.clone().requires_grad_(True)
+    pi, logp = Fo.tanh_gauss_head(mu, ls, eps, kr.TG_ACT_LIMIT, lo, hi,
+                                  det, wl)
+    assert (logp is None) == (not wl)
+    if dpi is None:
+        return pi.detach(), logp, None, None
+    seed = (pi * dpi).sum()
+    if wl:
+        seed = seed + (logp * dlogp).sum()
+    seed.backward()
+    # deterministic without logp: log_std reaches no output, its gradient
+    # is None where the kernel writes zeros
+    dls = ls.grad if ls.grad is not None else torch.zeros_like(ls)
+    return pi.detach(), logp, mu.grad, dls
+
+
+@pytest.mark.parametrize("clamp", kr.TGH_CLAMPS, ids=kr.tgh_id)
+@pytest.mark.parametrize("case", kr.TGH_CASES, ids=kr.tgh_id)
+def test_tgh_bounds_are_fair_and_eager_head_meets_them(case, clamp):
+    B, A = case
+    lo, hi = clamp
+    al = kr.TG_ACT_LIMIT
+    mu, ls, eps = kr.tgh_inputs(B, A, lo, hi)
+    dpi, dlogp = kr.tgh_bwd_operands(B, A)
+    for det, wl in TGH_VARIANTS:
+        tag = f"tgh {B}x{A} lo={lo} det={det} logp={wl}"
+        a = (mu, ls, eps, al, lo, hi, det, wl)
+        ref, bnd, out = kr.tgh_ref(*a), kr.tgh_fwd_bounds(*a), \
+            kr.tgh_fwd_f32(*a)
+        assert (ref[3] is None) == (not wl) and (out[3] is None) == (not wl)
+        names = ("pi", "prob", "ls_c") + (("logp",) if wl else ())
+        for nm, o, r, b in zip(names, out, ref, bnd):
+            _held(f"{tag} {nm}", o, r, b, 0.5)
+        assert torch.equal(out[2].double(), ref[2])
+        if det:
+            assert torch.equal(out[1], mu)
+        b_args = (mu, ls, eps, out[1], out[2], dpi, dlogp, al, lo, hi, det,
+                  wl)
+        ref_b, bnd_b = kr.tgh_bwd_ref(*b_args), kr.tgh_bwd_bounds(*b_args)
+        out_b = kr.tgh_bwd_f32(*b_args)
+        for nm, o, r, b in zip(("dmu", "dls"), out_b, ref_b, bnd_b):
+            _held(f"{tag} {nm}", o, r, b, 0.5)
+        outside = (ls < lo) | (ls > hi)
+        assert bool((ref_b[1][outside] == 0).all())
+        # the eager fallback: same reference, same bounds
+        pi_e, logp_e, dmu_e, dls_e = _eager_head(mu, ls, eps, lo, hi, det,
+                                                 wl, dpi, dlogp)
+        _held(f"{tag} eager pi", pi_e, ref[0], bnd[0])
+        if wl:
+            _held(f"{tag} eager logp", logp_e.detach(), ref[3], bnd[3])
+        # autograd differentiates the Jacobian term as written,
+        # d/dprob (prob + softplus(-2 prob)) = 1 - 2 sigmoid(-2 prob),
+        # where the kernel takes the closed form tanh(prob): near
+        # prob = 0 the difference cancels, so its error is absolute in
+        # |dlogp|: twice sigmoid's (one exp, a sum and a quotient) plus
+        # the roundings of the difference and of autograd's two
+        # accumulations into d prob, each on terms of at most |dlogp|
+        extra = torch.zeros(B, 1, dtype=torch.float64)
+        if wl:
+            extra = dlogp.double().abs()[:, None] \
+                * (2 * (kr.LIBM_TOL["exp"] + 2 * kr.U) + 4 * kr.U)
+        se = torch.zeros_like(extra) if det \
+            else (out[2].double().exp() * eps.double()).abs()
+        _held(f"{tag} eager dmu", dmu_e, ref_b[0], bnd_b[0] + extra)
+        _held(f"{tag} eager dls", dls_e, ref_b[1], bnd_b[1] + extra * se)
+        assert bool((dls_e[outside] == 0).all())
+
+
+def test_tgh_inputs_reach_the_small_std_cases():
+    """At the models' default clamp every |mu| in {0.5, 3, 12} meets every
+    log_std at or below -16 with |eps| >= 1, and there std * eps is lost
+    in mu + std * eps (prob == mu) although eps is not 0."""
+    lo, hi = kr.TGH_CLAMPS[1]
+    assert lo == -20.0
+    mu, ls, eps = kr.tgh_inputs(*kr.TGH_CASES[-1], lo, hi)
+    small = ls.clamp(lo, hi) <= kr.TGH_SMALL_LS
+    assert bool((eps[small].abs() >= 1).all())
+    pairs = {(abs(m), s) for m, s in zip(mu[small].tolist(),
+                                        ls[small].tolist())}
+    inside = float(torch.nextafter(torch.tensor(lo), torch.tensor(0.0)))
+    for m in (0.5, 3.0, 12.0):
+        for s in (lo - 1.0, lo, inside, -18.0, -16.0):
+            assert (m, s) in pairs, (m, s)
+    assert set(kr.tgh_raw_log_std(lo, hi)) <= set(ls.reshape(-1).tolist())
+    prob = mu + ls.clamp(lo, hi).exp() * eps
+    lost = (ls.clamp(lo, hi) <= -18.0) & (mu.abs() >= 3.0) \
+        & (eps.abs() < 4.0)
+    assert int(lost.sum()) > 100 and bool((prob[lost] == mu[lost]).all())
+    assert bool((eps[lost] != 0).all())
+    # the three small cases cover the special values between them
+    for c in kr.TGH_CLAMPS:
+        seen = set()
+        for B, A in kr.TGH_CASES[:-1]:
+            assert A <= 64
+            seen |= set(kr.tgh_inputs(B, A, *c)[1].reshape(-1).tolist())
+        assert set(torch.tensor(kr.tgh_raw_log_std(*c)).tolist()) <= seen
+
+
+@pytest.mark.parametrize("case", kr.TGH_CASES[1:], ids=kr.tgh_id)
+def test_logp_rebuilt_by_subtraction_misses_at_the_default_clamp(case):
+    """What the default-clamp cases are for: logp with the noise rebuilt
+    as (prob - mu) / std, the head's earlier order, stays inside the bound
+    at the clamp of -5 and misses it by orders of magnitude at -20."""
+    B, A = case
+    al = kr.TG_ACT_LIMIT
+    for (lo, hi), misses in zip(kr.TGH_CLAMPS, (False, True)):
+        mu, ls, eps = kr.tgh_inputs(B, A, lo, hi)
+        a = (mu, ls, eps, al, lo, hi, False, True)
+        ref, bnd = kr.tgh_ref(*a), kr.tgh_fwd_bounds(*a)
+        old = kr.tgh_logp_by_subtraction_f32(mu, ls, eps, lo, hi)
+        r = _worst(f"subtractive logp {B}x{A} lo={lo}", old, ref[3], bnd[3])
+        assert (r > 100.0) if misses else (r <= 1.0), (lo, r)
+
+
+def _q_leaves(t):
+    """(q1, q2) as leaves for the eager losses under autograd."""
+    return (t["q1"].clone().requires_grad_(True),
+            t["q2"].clone().requires_grad_(True))
+
+
+@pytest.mark.parametrize("B", kr.FLAT_LOSS_B)
+def test_flat_loss_bounds_are_fair_and_eager_losses_meet_them(B):
+    from torch_actor_critic_amd.ops import functional as Fo
+    h = kr.QLOSS_HYPER
+    hs = (h["alpha"], h["gamma"], h["scale"])
+    t = kr.flat_qloss_inputs(B)
+    if B >= 15:
+        fr = torch.tensor(kr.FLAT_DONE_FRACTIONS, dtype=torch.float32)
+        assert set(fr.tolist()) | {0.0, 1.0} <= set(t["done"].tolist())
+        assert int((t["q1t"] == t["q2t"]).sum()) >= B // 3
+        frac = (t["done"] != 0) & (t["done"] != 1)
+        assert int(frac.sum()) >= B // 5
+    ref, bnd = kr.qloss_ref(t, B, *hs)
+    out = kr.qloss_f32(t, B, *hs)
+    for k in ("loss", "dq1", "dq2"):
+        _held(f"flat qloss B={B} {k}", out[k], ref[k], bnd[k], 0.5)
+    q1, q2 = _q_leaves(t)
+    loss = Fo.sac_q_loss(q1, q2, t["q1t"], t["q2t"], t["logp"], t["rew"],
+                         t["done"], *hs)
+    loss.backward()
+    _held(f"eager qloss B={B} loss", loss.detach(), ref["loss"], bnd["loss"])
+    _held(f"eager qloss B={B} dq1", q1.grad, ref["dq1"], bnd["dq1"])
+    _held(f"eager qloss B={B} dq2", q2.grad, ref["dq2"], bnd["dq2"])
+
+    t = kr.piloss_inputs(B, 1, seed=31)
+    ref, bnd = kr.piloss_ref(t, B, h["alpha"])
+    out = kr.piloss_f32(t, B, h["alpha"])
+    _held(f"flat piloss B={B} loss", out["loss"], ref["loss"], bnd["loss"],
+          0.5)
+    for k in ("dq1", "dq2"):
+        assert torch.equal(out[k].double(), ref[k].float().double()), k
+    dl = kr.piloss_dlogp_ref(B, h["alpha"])
+    assert abs(dl - 0.2 / B) <= kr.E32 * dl
+    q1, q2 = _q_leaves(t)
+    logp = t["logp"].clone().requires_grad_(True)
+    loss = Fo.sac_pi_loss(q1, q2, logp, h["alpha"])
+    loss.backward()
+    _held(f"eager piloss B={B} loss", loss.detach(), ref["loss"],
+          bnd["loss"])
+    _held(f"eager piloss B={B} dq1", q1.grad, ref["dq1"], bnd["dq1"])
+    _held(f"eager piloss B={B} dq2", q2.grad, ref["dq2"], bnd["dq2"])
+    _held(f"eager piloss B={B} dlogp", logp.grad,
+          torch.full((B,), dl, dtype=torch.float64), kr.U * dl)
+    tie = t["q1"] == t["q2"]
+    assert bool(tie.any())
+    assert torch.equal(q1.grad[tie], q2.grad[tie])
+
+
+@pytest.mark.parametrize("rho", kr.POLYAK_RHO)
+def test_polyak_bound_is_fair_and_eager_polyak_meets_it(rho):
+    from torch_actor_critic_amd.ops import functional as Fo
+    for n in kr.POLYAK_N[:-1] + [20000]:
+        targ, src = kr.polyak_inputs(n)
+        ref, bnd = kr.polyak_ref(targ, src, rho)
+        _held(f"polyak n={n} rho={rho}", kr.polyak_f32(targ, src, rho), ref,
+              bnd, 0.5)
+        got, s0 = targ.clone(), src.clone()
+        Fo.polyak_(got, src, rho)
+        _held(f"eager polyak n={n} rho={rho}", got, ref, bnd)
+        assert torch.equal(src, s0)
+        if rho in (0.0, 1.0):
+            assert torch.equal(got, src if rho == 0.0 else targ)
+        # a dropped element (target left as it was) is far outside
+        if rho == 0.995 and n > 100:
+            assert float(((targ.double() - ref).abs() / bnd).median()) > 1000
+
+
+@pytest.mark.parametrize("wd", kr.ADAM_FLAT_WD)
+@pytest.mark.parametrize("step", kr.ADAM_FLAT_STEPS)
+def test_adam_flat_bounds_are_fair_and_eager_adam_meets_them(step, wd):
+    """adam_kernel's order (no FMA) under half of adam_bounds, weight decay
+    included, and the eager branch of Fo.adam_step_ under the bounds."""
+    from torch_actor_critic_amd.ops import functional as Fo
+    hyper = dict(kr.ADAM_HYPER, wd=wd)
+    p, g, m, v, _ = kr.adam_state(20000, step, False, seed=step)
+    ref = kr.adam_ref(p, g, m, v, None, step, hyper)
+    bounds = kr.adam_bounds(p, g, m, ref, hyper)
+    outs = kr.adam_flat_f32(p, g, m, v, step, hyper)
+    for nm, o, r, b in zip("pmv", outs, ref, bounds):
+        _held(f"adam_flat step={step} wd={wd} {nm}", o, r, b, 0.5)
+    pe, me, ve = p.clone(), m.clone(), v.clone()
+    ctr = torch.tensor([step - 1])
+    Fo.adam_step_(pe, g, me, ve, ctr, hyper["lr"], hyper["b1"], hyper["b2"],
+                  hyper["eps"], wd)
+    assert int(ctr) == step
+    for nm, o, r, b in zip("pmv", (pe, me, ve), ref, bounds):
+        _held(f"eager adam step={step} wd={wd} {nm}", o, r, b)
+    if wd:
+        # the decay is visible in m: without it m is off by (1 - b1) wd p
+        no_wd = kr.adam_ref(p, g, m, v, None, step, dict(hyper, wd=0.0))
+        assert float(((no_wd[1] - ref[1]).abs() / bounds[1]).median()) > 100

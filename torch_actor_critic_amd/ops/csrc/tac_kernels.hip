@@ -516,12 +516,15 @@ void tanh_gauss_fwd_kernel(const float* __restrict__ mu,
     float m = mu[i];
     float ls = fminf(fmaxf(log_std[i], lo), hi);
     float std = expf(ls);
-    float prob = DET ? m : m + std * eps[i];
+    // the noise itself, not (prob - m) / std: at a small std the sum
+    // m + std * e rounds back to m and the quotient loses e (same
+    // operation order as tg_fwd2_kernel, fused.hip)
+    float e = DET ? 0.f : eps[i];
+    float prob = DET ? m : m + std * e;
     pi[i] = tanhf(prob) * act_limit;
     prob_out[i] = prob;
     ls_c_out[i] = ls;
     if constexpr (WITH_LOGP) {
-      float e = (prob - m) / std;
       float gauss = -0.5f * e * e - ls - 0.5f * kLog2Pi;
       float corr = kTwoLog2 - prob - softplus_neg2(prob);
       acc = gauss - corr;
@@ -1321,6 +1324,54 @@ inline hipStream_t cur_stream() {
   TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dtype() == torch::kFloat32, \
               #x " must be contiguous fp32 CUDA tensor")
 
+// Host gates of the flat bindings: every tensor is contiguous fp32 on the
+// device of the first one, with exactly the expected sizes; the message
+// names the binding.
+inline void need_flat(const torch::Tensor& t, const torch::Tensor& first,
+                      at::IntArrayRef sizes, const char* fn,
+                      const char* name) {
+  TORCH_CHECK(t.defined() && t.is_cuda() && t.is_contiguous() &&
+                  t.scalar_type() == torch::kFloat32,
+              fn, ": ", name, " must be a contiguous fp32 GPU tensor");
+  TORCH_CHECK(t.device() == first.device(), fn, ": ", name,
+              " is on another device than the first argument");
+  TORCH_CHECK(t.sizes() == sizes, fn, ": ", name, " has sizes ", t.sizes(),
+              ", expected ", sizes);
+}
+
+// [B, A] of the head's first tensor; A <= 64 (one wave per row).
+inline void need_head(const torch::Tensor& t, const char* fn,
+                      const char* name) {
+  TORCH_CHECK(t.defined() && t.is_cuda() && t.is_contiguous() &&
+                  t.scalar_type() == torch::kFloat32 && t.dim() == 2,
+              fn, ": ", name, " must be a contiguous fp32 GPU tensor [B, A]");
+  TORCH_CHECK(t.size(1) <= 64, fn, ": act_dim ", t.size(1),
+              " > 64 not supported by fused head");
+  TORCH_CHECK(t.size(0) < (int64_t(1) << 31) / 64, fn, ": B too large");
+}
+
+// [B] of the losses' first tensor.
+inline void need_vec(const torch::Tensor& t, const char* fn,
+                     const char* name) {
+  TORCH_CHECK(t.defined() && t.is_cuda() && t.is_contiguous() &&
+                  t.scalar_type() == torch::kFloat32 && t.dim() == 1,
+              fn, ": ", name, " must be a contiguous fp32 GPU tensor [B]");
+  TORCH_CHECK(t.size(0) < (int64_t(1) << 31) - 64 * 256, fn,
+              ": B too large");
+}
+
+// A flat buffer as long as the first one (polyak_, adam_step_).
+inline void need_numel(const torch::Tensor& t, const torch::Tensor& first,
+                       const char* fn, const char* name) {
+  TORCH_CHECK(t.defined() && t.is_cuda() && t.is_contiguous() &&
+                  t.scalar_type() == torch::kFloat32,
+              fn, ": ", name, " must be a contiguous fp32 GPU tensor");
+  TORCH_CHECK(t.device() == first.device(), fn, ": ", name,
+              " is on another device than the first argument");
+  TORCH_CHECK(t.numel() == first.numel(), fn, ": ", name, " has ",
+              t.numel(), " elements, expected ", first.numel());
+}
+
 bool g_bf16 = false;  // compute mode: bf16 MFMA inputs (fp32 master data)
 
 void set_compute_bf16(bool on) { g_bf16 = on; }
@@ -1403,13 +1454,16 @@ std::vector<torch::Tensor> tanh_gauss_fwd(torch::Tensor mu,
                                           double lo, double hi,
                                           bool deterministic,
                                           bool with_logprob) {
-  CHECK_IN(mu); CHECK_IN(log_std); CHECK_IN(eps);
+  need_head(mu, "tanh_gauss_fwd", "mu");
+  need_flat(log_std, mu, mu.sizes(), "tanh_gauss_fwd", "log_std");
+  need_flat(eps, mu, mu.sizes(), "tanh_gauss_fwd", "eps");
   const int B = mu.size(0), A = mu.size(1);
-  TORCH_CHECK(A <= 64, "act_dim > 64 not supported by fused head");
   auto pi = torch::empty_like(mu);
   auto prob = torch::empty_like(mu);
   auto ls_c = torch::empty_like(mu);
   auto logp = torch::empty({B}, mu.options());
+  if (B == 0) return {pi, logp, prob, ls_c};
+  if (A == 0) { logp.zero_(); return {pi, logp, prob, ls_c}; }
   auto s = cur_stream();
   auto launch = [&](auto det_c, auto wl_c) {
     hipLaunchKernelGGL(
@@ -1439,10 +1493,17 @@ std::vector<torch::Tensor> tanh_gauss_bwd(torch::Tensor dpi,
                                           double act_limit, double lo,
                                           double hi, bool deterministic,
                                           bool with_logprob) {
-  CHECK_IN(dpi); CHECK_IN(mu);
+  need_head(mu, "tanh_gauss_bwd", "mu");
+  need_flat(dpi, mu, mu.sizes(), "tanh_gauss_bwd", "dpi");
+  need_flat(dlogp, mu, {mu.size(0)}, "tanh_gauss_bwd", "dlogp");
+  need_flat(log_std, mu, mu.sizes(), "tanh_gauss_bwd", "log_std");
+  need_flat(eps, mu, mu.sizes(), "tanh_gauss_bwd", "eps");
+  need_flat(prob, mu, mu.sizes(), "tanh_gauss_bwd", "prob");
+  need_flat(ls_c, mu, mu.sizes(), "tanh_gauss_bwd", "ls_c");
   const int B = mu.size(0), A = mu.size(1);
   auto dmu = torch::empty_like(mu);
   auto dls = torch::empty_like(mu);
+  if (mu.numel() == 0) return {dmu, dls};
   auto s = cur_stream();
   auto launch = [&](auto det_c) {
     hipLaunchKernelGGL(
@@ -1464,11 +1525,18 @@ std::vector<torch::Tensor> sac_q_loss_fwd(torch::Tensor q1, torch::Tensor q2,
                                           torch::Tensor logp, torch::Tensor rew,
                                           torch::Tensor done, double alpha,
                                           double gamma, double scale) {
-  CHECK_IN(q1); CHECK_IN(q2);
+  need_vec(q1, "sac_q_loss_fwd", "q1");
+  need_flat(q2, q1, q1.sizes(), "sac_q_loss_fwd", "q2");
+  need_flat(q1t, q1, q1.sizes(), "sac_q_loss_fwd", "q1t");
+  need_flat(q2t, q1, q1.sizes(), "sac_q_loss_fwd", "q2t");
+  need_flat(logp, q1, q1.sizes(), "sac_q_loss_fwd", "logp");
+  need_flat(rew, q1, q1.sizes(), "sac_q_loss_fwd", "rew");
+  need_flat(done, q1, q1.sizes(), "sac_q_loss_fwd", "done");
   const int B = q1.size(0);
   auto loss = torch::zeros({}, q1.options());
   auto dq1 = torch::empty_like(q1);
   auto dq2 = torch::empty_like(q2);
+  if (B == 0) return {loss, dq1, dq2};
   int blocks = std::min((B + 255) / 256, 64);
   hipLaunchKernelGGL(sac_q_loss_kernel, dim3(blocks), dim3(256), 0,
                      cur_stream(),
@@ -1483,12 +1551,15 @@ std::vector<torch::Tensor> sac_q_loss_fwd(torch::Tensor q1, torch::Tensor q2,
 
 std::vector<torch::Tensor> sac_pi_loss_fwd(torch::Tensor q1, torch::Tensor q2,
                                            torch::Tensor logp, double alpha) {
-  CHECK_IN(q1); CHECK_IN(q2); CHECK_IN(logp);
+  need_vec(q1, "sac_pi_loss_fwd", "q1");
+  need_flat(q2, q1, q1.sizes(), "sac_pi_loss_fwd", "q2");
+  need_flat(logp, q1, q1.sizes(), "sac_pi_loss_fwd", "logp");
   const int B = q1.size(0);
   auto loss = torch::zeros({}, q1.options());
   auto dq1 = torch::empty_like(q1);
   auto dq2 = torch::empty_like(q2);
   auto dlogp = torch::empty_like(logp);
+  if (B == 0) return {loss, dq1, dq2, dlogp};
   int blocks = std::min((B + 255) / 256, 64);
   hipLaunchKernelGGL(sac_pi_loss_kernel, dim3(blocks), dim3(256), 0,
                      cur_stream(),
@@ -1500,8 +1571,12 @@ std::vector<torch::Tensor> sac_pi_loss_fwd(torch::Tensor q1, torch::Tensor q2,
 }
 
 void polyak_(torch::Tensor targ, torch::Tensor src, double rho) {
-  CHECK_IN(targ); CHECK_IN(src);
+  TORCH_CHECK(targ.defined() && targ.is_cuda() && targ.is_contiguous() &&
+                  targ.scalar_type() == torch::kFloat32,
+              "polyak_: targ must be a contiguous fp32 GPU tensor");
+  need_numel(src, targ, "polyak_", "src");
   int64_t n = targ.numel();
+  if (n == 0) return;
   int blocks = (int)std::min<int64_t>((n / 4 + 255) / 256 + 1, 1024);
   hipLaunchKernelGGL(polyak_kernel, dim3(blocks), dim3(256), 0, cur_stream(),
                      targ.data_ptr<float>(), src.data_ptr<float>(), n,
@@ -1511,8 +1586,19 @@ void polyak_(torch::Tensor targ, torch::Tensor src, double rho) {
 void adam_step_(torch::Tensor p, torch::Tensor g, torch::Tensor m,
                 torch::Tensor v, torch::Tensor step, double lr, double b1,
                 double b2, double eps, double wd) {
-  CHECK_IN(p); CHECK_IN(g); CHECK_IN(m); CHECK_IN(v);
+  TORCH_CHECK(p.defined() && p.is_cuda() && p.is_contiguous() &&
+                  p.scalar_type() == torch::kFloat32,
+              "adam_step_: p must be a contiguous fp32 GPU tensor");
+  need_numel(g, p, "adam_step_", "g");
+  need_numel(m, p, "adam_step_", "m");
+  need_numel(v, p, "adam_step_", "v");
+  TORCH_CHECK(step.defined() && step.is_cuda() &&
+                  step.scalar_type() == torch::kInt64 && step.numel() == 1 &&
+                  step.device() == p.device(),
+              "adam_step_: step must be a one-element int64 tensor on the "
+              "GPU of p");
   int64_t n = p.numel();
+  if (n == 0) return;
   auto s = cur_stream();
   hipLaunchKernelGGL(bump_counter_kernel, dim3(1), dim3(1), 0, s,
                      step.data_ptr<int64_t>());

@@ -153,6 +153,71 @@ def _direct_outs(pairs):
     return outs
 
 
+def _only_needed(ctx, first, grads):
+    """`grads` for the inputs first, first + 1, ...: None wherever the
+    input needs no gradient (what plain autograd would return)."""
+    return tuple(g if ctx.needs_input_grad[first + i] else None
+                 for i, g in enumerate(grads))
+
+
+def _twin_backward(ctx, ix, iw, dy1, dy2):
+    """Backward of a twin (live) pair of dense layers, shared by
+    _PairedLinear and _QuadLinear: ix / iw are the positions of x1 and w1
+    among the Function's inputs (x1, x2 and w1, b1, w2, b2 are adjacent).
+    Each launch serves a group of inputs and runs when any member needs a
+    gradient; members that need none get None.  A dy of None (an output
+    the backward pass never reached) counts as zeros.  Returns
+    (dx1, dx2, dw1, db1, dw2, db2)."""
+    x1, x2, w1, w2, y1, y2, b1, b2 = ctx.saved_tensors
+    if dy1 is None and dy2 is None:
+        return (None,) * 6
+    ext = require_extension()
+    dy1 = torch.zeros_like(y1) if dy1 is None else dy1.contiguous()
+    dy2 = torch.zeros_like(y2) if dy2 is None else dy2.contiguous()
+    M, K = x1.shape
+    N = w1.shape[0]
+    m1 = y1 if ctx.relu else None
+    m2 = y2 if ctx.relu else None
+    dw1 = dw2 = db1 = db2 = None
+    if any(ctx.needs_input_grad[iw:iw + 4]):
+        outs = _direct_outs([(w1, b1), (w2, b2)])
+        if outs is None:
+            dw1 = torch.empty_like(w1)
+            dw2 = torch.empty_like(w2)
+            db1 = torch.empty(N, device=w1.device, dtype=w1.dtype)
+            db2 = torch.empty_like(db1)
+            gws = (dw1, db1, dw2, db2)
+        else:
+            (gw1, gb1), (gw2, gb2) = outs
+            if gb1 is None:
+                gb1 = torch.empty(0, device=w1.device, dtype=w1.dtype)
+            if gb2 is None:
+                gb2 = torch.empty(0, device=w1.device, dtype=w1.dtype)
+            gws = (gw1, gb1, gw2, gb2)
+        ext.mwgrad([dy1, dy2], [m1, m2], [x1, x2],
+                   [gws[0], gws[2]], [gws[1], gws[3]],
+                   M, N, K, N, K, 0)
+        dw1, db1, dw2, db2 = _only_needed(ctx, iw, (dw1, db1, dw2, db2))
+    dx1 = dx2 = None
+    if ctx.needs_input_grad[ix] or ctx.needs_input_grad[ix + 1]:
+        wt1 = _dense_wt(ext, w1)
+        wt2 = _dense_wt(ext, w2)
+        dx1 = torch.empty_like(x1)
+        if ctx.shared_x:
+            # both critics share the input: dx = dy1@wt1 + dy2@wt2
+            # in ONE sum2 GEMM launch; autograd sees dx2=None so no
+            # accumulate-add kernel runs
+            ext.mgemm([dy1], [wt1], [None], [dx1], [m1], M, K, N, N,
+                      K, False, [dy2], [wt2], [m2], N, 0, 0, [])
+        else:
+            dx2 = torch.empty_like(x2)
+            ext.mgemm([dy1, dy2], [wt1, wt2], [None, None],
+                      [dx1, dx2], [m1, m2], M, K, N, N, K, False,
+                      [], [], [], 0, 0, 0, [])
+            dx1, dx2 = _only_needed(ctx, ix, (dx1, dx2))
+    return dx1, dx2, dw1, db1, dw2, db2
+
+
 # ---------------------------------------------------------------------------
 # Linear (+ optional ReLU)
 # ---------------------------------------------------------------------------
@@ -183,7 +248,8 @@ class _NativeLinear(torch.autograd.Function):
         N = w.shape[0]
         ymask = y if ctx.relu else None
         dw = db = None
-        if ctx.needs_input_grad[1]:
+        # the wgrad launch serves w and b: run it when either needs it
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
             outs = _direct_outs([(w, b)])
             if outs is None:
                 dw = torch.empty_like(w)
@@ -197,6 +263,7 @@ class _NativeLinear(torch.autograd.Function):
             ext.mwgrad([dy], [ymask], [x], [dw], [db], M, N, K, N, K, 0)
             if outs is not None:
                 dw = db = None
+            dw, db = _only_needed(ctx, 1, (dw, db))
         dx = None
         if ctx.needs_input_grad[0]:
             wt = _dense_wt(ext, w)
@@ -320,49 +387,7 @@ class _PairedLinear(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy1, dy2):
-        x1, x2, w1, w2, y1, y2, b1, b2 = ctx.saved_tensors
-        ext = require_extension()
-        dy1 = dy1.contiguous()
-        dy2 = dy2.contiguous()
-        M, K = x1.shape
-        N = w1.shape[0]
-        m1 = y1 if ctx.relu else None
-        m2 = y2 if ctx.relu else None
-        dw1 = dw2 = db1 = db2 = None
-        if ctx.needs_input_grad[2]:
-            outs = _direct_outs([(w1, b1), (w2, b2)])
-            if outs is None:
-                dw1 = torch.empty_like(w1)
-                dw2 = torch.empty_like(w2)
-                db1 = torch.empty(N, device=w1.device, dtype=w1.dtype)
-                db2 = torch.empty_like(db1)
-                gws = (dw1, db1, dw2, db2)
-            else:
-                (gw1, gb1), (gw2, gb2) = outs
-                if gb1 is None:
-                    gb1 = torch.empty(0, device=w1.device, dtype=w1.dtype)
-                    gb2 = torch.empty_like(gb1)
-                gws = (gw1, gb1, gw2, gb2)
-            ext.mwgrad([dy1, dy2], [m1, m2], [x1, x2],
-                       [gws[0], gws[2]], [gws[1], gws[3]],
-                       M, N, K, N, K, 0)
-        dx1 = dx2 = None
-        if ctx.needs_input_grad[0]:
-            wt1 = _dense_wt(ext, w1)
-            wt2 = _dense_wt(ext, w2)
-            dx1 = torch.empty_like(x1)
-            if ctx.shared_x:
-                # both critics share the input: dx = dy1@wt1 + dy2@wt2
-                # in ONE sum2 GEMM launch; autograd sees dx2=None so no
-                # accumulate-add kernel runs
-                ext.mgemm([dy1], [wt1], [None], [dx1], [m1], M, K, N, N,
-                          K, False, [dy2], [wt2], [m2], N, 0, 0, [])
-            else:
-                dx2 = torch.empty_like(x2)
-                ext.mgemm([dy1, dy2], [wt1, wt2], [None, None],
-                          [dx1, dx2], [m1, m2], M, K, N, N, K, False,
-                          [], [], [], 0, 0, 0, [])
-        return dx1, dx2, dw1, db1, dw2, db2, None
+        return _twin_backward(ctx, 0, 2, dy1, dy2) + (None,)
 
 
 def linear_pair(x1, x2, w1, b1, w2, b2, relu: bool):
@@ -472,45 +497,7 @@ class _QuadLinear(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dyt1, dyt2, dy1, dy2):
-        x1, x2, w1, w2, y1, y2, b1, b2 = ctx.saved_tensors
-        ext = require_extension()
-        dy1 = dy1.contiguous()
-        dy2 = dy2.contiguous()
-        M, K = x1.shape
-        N = w1.shape[0]
-        m1 = y1 if ctx.relu else None
-        m2 = y2 if ctx.relu else None
-        dw1 = dw2 = db1 = db2 = None
-        if ctx.needs_input_grad[8]:
-            outs = _direct_outs([(w1, b1), (w2, b2)])
-            if outs is None:
-                dw1 = torch.empty_like(w1)
-                dw2 = torch.empty_like(w2)
-                db1 = torch.empty(N, device=w1.device, dtype=w1.dtype)
-                db2 = torch.empty_like(db1)
-                gws = (dw1, db1, dw2, db2)
-            else:
-                (gw1, gb1), (gw2, gb2) = outs
-                if gb1 is None:
-                    gb1 = torch.empty(0, device=w1.device, dtype=w1.dtype)
-                    gb2 = torch.empty_like(gb1)
-                gws = (gw1, gb1, gw2, gb2)
-            ext.mwgrad([dy1, dy2], [m1, m2], [x1, x2],
-                       [gws[0], gws[2]], [gws[1], gws[3]],
-                       M, N, K, N, K, 0)
-        dx1 = dx2 = None
-        if ctx.needs_input_grad[2]:
-            wt1 = _dense_wt(ext, w1)
-            wt2 = _dense_wt(ext, w2)
-            dx1 = torch.empty_like(x1)
-            if ctx.shared_x:
-                ext.mgemm([dy1], [wt1], [None], [dx1], [m1], M, K, N, N,
-                          K, False, [dy2], [wt2], [m2], N, 0, 0, [])
-            else:
-                dx2 = torch.empty_like(x2)
-                ext.mgemm([dy1, dy2], [wt1, wt2], [None, None],
-                          [dx1, dx2], [m1, m2], M, K, N, N, K, False,
-                          [], [], [], 0, 0, 0, [])
+        dx1, dx2, dw1, db1, dw2, db2 = _twin_backward(ctx, 2, 8, dy1, dy2)
         return (None, None, dx1, dx2, None, None, None, None,
                 dw1, db1, dw2, db2, None)
 
@@ -601,8 +588,14 @@ def _eager_tanh_gauss(mu, log_std, eps, act_limit, log_min_std, log_max_std,
     pi_action = torch.tanh(prob) * act_limit
     logprob = None
     if with_logprob:
-        # N(mu, std).log_prob(prob) with prob = mu + std*eps
-        gauss = -0.5 * ((prob - mu) / std) ** 2 - log_std - 0.5 * _LOG_2PI
+        # N(mu, std).log_prob(prob) with prob = mu + std*eps: the
+        # standardised residual (prob - mu) / std IS eps (0 when
+        # deterministic); rebuilding it by subtraction loses it at a small
+        # std, where mu + std*eps rounds back to mu (DEVIATIONS.md)
+        if deterministic:
+            gauss = -log_std - 0.5 * _LOG_2PI
+        else:
+            gauss = -0.5 * eps * eps - log_std - 0.5 * _LOG_2PI
         logprob = gauss.sum(dim=-1)
         # numerically-stable tanh Jacobian correction
         logprob = logprob - (_2LOG2 - prob - F.softplus(-2.0 * prob)).sum(dim=-1)
@@ -726,6 +719,11 @@ def sac_pi_loss(q1, q2, logp, alpha):
 # Flat-buffer maintenance ops (no autograd)
 # ---------------------------------------------------------------------------
 
+def _as_f32(v: float) -> float:
+    """A Python scalar rounded to fp32, as a kernel argument is."""
+    return float(torch.tensor(v, dtype=torch.float32))
+
+
 def polyak_(flat_target: torch.Tensor, flat_src: torch.Tensor, polyak: float):
     """In-place: target = polyak*target + (1-polyak)*src — ONE kernel over
     the module's whole flattened parameter buffer (the reference loops
@@ -733,7 +731,9 @@ def polyak_(flat_target: torch.Tensor, flat_src: torch.Tensor, polyak: float):
     if use_native(flat_target, flat_src):
         require_extension().polyak_(flat_target, flat_src, polyak)
     else:
-        flat_target.mul_(polyak).add_(flat_src, alpha=1.0 - polyak)
+        # rho as the kernel holds it (fp32), so 1 - rho is the kernel's too
+        rho = _as_f32(polyak)
+        flat_target.mul_(rho).add_(flat_src, alpha=1.0 - rho)
 
 
 def adam_step_(p, g, m, v, step_t, lr, beta1, beta2, eps, weight_decay=0.0):
@@ -745,6 +745,9 @@ def adam_step_(p, g, m, v, step_t, lr, beta1, beta2, eps, weight_decay=0.0):
     else:
         step_t += 1
         step = int(step_t.item())
+        # the betas as the kernel holds them (fp32): 1 - 0.999f differs
+        # from fp32(0.001) by 1.3e-5 relative
+        beta1, beta2 = _as_f32(beta1), _as_f32(beta2)
         if weight_decay != 0.0:
             g = g.add(p, alpha=weight_decay)
         m.mul_(beta1).add_(g, alpha=1.0 - beta1)
