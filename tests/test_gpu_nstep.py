@@ -1,4 +1,5 @@
-"""N-step gather kernels (replay_gather_n_kernel, gather2n_kernel) against
+"""N-step gathers (replay_sample_into_n and gather2n: the flat and concat
+instantiations of replay_draw.h::gather_kernel<Draw::UniformN>) against
 ``ReplayBuffer.sample_at`` on the ring fixture of tests/test_nstep.py.
 
 ``state[:, 0]`` of a sampled row is the global step t, so the slot the

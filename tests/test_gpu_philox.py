@@ -1,5 +1,5 @@
-"""The two device copies of Philox4x32-10 (tac_kernels.hip::philox4,
-fused.hip::philox_) and every draw built on them, against the host
+"""The device Philox4x32-10 (replay_draw.h::philox4, as tac_kernels.hip and
+fused.hip each compiled it) and every draw built on it, against the host
 generator of kernel_refs.py, which test_kernel_refs.py holds to the
 published known-answer vectors.
 

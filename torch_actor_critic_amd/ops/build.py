@@ -27,6 +27,14 @@ def build(verbose: bool = False) -> str:
     sources = sorted(glob.glob(os.path.join(_CSRC, "*.hip")))
     assert sources, "no HIP sources found"
 
+    # the generated ninja rule for .hip sources records no header
+    # dependencies: drop the objects an edited header has left stale
+    newest = max(map(os.path.getmtime, glob.glob(os.path.join(_CSRC, "*.h"))),
+                 default=0.0)
+    for obj in glob.glob(os.path.join(_BUILD, "*.o")):
+        if os.path.getmtime(obj) < newest:
+            os.remove(obj)
+
     cpp_extension.load(
         name="_tac_hip",
         sources=sources,

@@ -29,55 +29,21 @@
 #include <utility>
 #include <vector>
 
+#include "replay_draw.h"
+
 namespace fused {
 
-#define DEVINL __device__ __forceinline__
+using namespace replay;
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 
-// ---------------------------------------------------------------------------
-// Philox (same generator as tac_kernels.hip; duplicated in this TU to keep
-// both translation units self-contained)
-// ---------------------------------------------------------------------------
-
-struct P4 { uint32_t x, y, z, w; };
-
-DEVINL uint32_t mulhilo_(uint32_t a, uint32_t b, uint32_t* hi) {
-  uint64_t p = (uint64_t)a * (uint64_t)b;
-  *hi = (uint32_t)(p >> 32);
-  return (uint32_t)p;
-}
-
-DEVINL P4 philox_(uint64_t seed, uint64_t chi, uint64_t clo) {
-  uint32_t c0 = (uint32_t)clo, c1 = (uint32_t)(clo >> 32);
-  uint32_t c2 = (uint32_t)chi, c3 = (uint32_t)(chi >> 32);
-  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    uint32_t h0, h1;
-    uint32_t l0 = mulhilo_(0xD2511F53u, c0, &h0);
-    uint32_t l1 = mulhilo_(0xCD9E8D57u, c2, &h1);
-    uint32_t n0 = h1 ^ c1 ^ k0, n1 = l1, n2 = h0 ^ c3 ^ k1, n3 = l0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  return {c0, c1, c2, c3};
-}
-
-// Debug/test helper: the four raw output words of subsequences
-// clo0 .. clo0 + n - 1, so the generator itself can be held against a
-// host implementation (tests/kernel_refs.py::philox4x32).
+// Debug/test helper: the raw Philox words of subsequences clo0 ..
+// clo0 + n - 1 as this translation unit compiled the generator.
 __global__ __launch_bounds__(256)
 void philox_words2_kernel(int64_t* __restrict__ out, uint64_t seed,
                           uint64_t chi, uint64_t clo0, int64_t n) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  P4 r = philox_(seed, chi, clo0 + (uint64_t)i);
-  out[4 * i + 0] = (int64_t)r.x;
-  out[4 * i + 1] = (int64_t)r.y;
-  out[4 * i + 2] = (int64_t)r.z;
-  out[4 * i + 3] = (int64_t)r.w;
+  philox_words_row(out, seed, chi, clo0, n);
 }
 
 // ---------------------------------------------------------------------------
@@ -1559,283 +1525,10 @@ void transpose_multi_kernel(TArgs t) {
 }
 
 // ---------------------------------------------------------------------------
-// Replay gather writing straight into the concat-layout batch buffers
+// Prioritized replay: maintenance of the fan-out-64 sum tree the gather
+// draws from (replay_draw.h has the layout and the draw;
+// buffer/replay.py::_update_priorities_ref is the executable definition)
 // ---------------------------------------------------------------------------
-
-__global__ __launch_bounds__(256)
-void gather2_kernel(const float* __restrict__ state,
-                    const float* __restrict__ act,
-                    const float* __restrict__ rew,
-                    const float* __restrict__ nstate,
-                    const float* __restrict__ done,
-                    const int64_t* __restrict__ size_dev,
-                    const int64_t* __restrict__ ctr, int64_t ctr_add,
-                    uint64_t seed,
-                    float* __restrict__ xc,   // [2B, ldc]
-                    float* __restrict__ xc2,  // [B, ldc]
-                    float* __restrict__ orew, float* __restrict__ od,
-                    int B, int obs_dim, int act_dim, int ldc) {
-  const int j = blockIdx.x;
-  const uint64_t size = (uint64_t)size_dev[0];
-  P4 r = philox_(seed, (uint64_t)(ctr[0] + ctr_add), (uint64_t)j);
-  uint64_t u = ((uint64_t)r.x << 32) | r.y;
-  int64_t idx = (int64_t)(u % (size ? size : 1));
-
-  const float* srow = state + idx * obs_dim;
-  const float* nrow = nstate + idx * obs_dim;
-  const float* arow = act + idx * act_dim;
-  for (int c = threadIdx.x; c < obs_dim; c += blockDim.x) {
-    float s = srow[c];
-    xc[(int64_t)j * ldc + c] = s;           // s -> XC rows :B
-    xc2[(int64_t)j * ldc + c] = s;          // s -> XC2
-    xc[(int64_t)(B + j) * ldc + c] = nrow[c];  // ns -> XC rows B:
-  }
-  for (int c = threadIdx.x; c < act_dim; c += blockDim.x)
-    xc[(int64_t)j * ldc + obs_dim + c] = arow[c];  // a -> XC rows :B
-  if (threadIdx.x == 0) {
-    orew[j] = rew[idx];
-    od[j] = done[idx];
-  }
-}
-
-// N-step window walk — same code as tac_kernels.hip::nstep_walk (see the
-// comment there), duplicated to keep both translation units self-contained.
-// Run by ONE full wave; lane m < n loads slot (idx+m) % cap, a ballot finds
-// the first lane that closes the window, the discounted sum is added in
-// ascending m with contraction off.  All lanes return the same values.
-DEVINL int64_t nstep_walk_(const float* __restrict__ rew,
-                           const float* __restrict__ done,
-                           const float* __restrict__ ep_end, int64_t idx,
-                           int64_t cap, int64_t newest, int n, float gamma,
-                           float* R, float* deff) {
-#pragma clang fp contract(off)
-  const int lane = threadIdx.x & 63;
-  const int64_t slot = (idx + lane) % cap;
-  float r = 0.f, d = 0.f;
-  bool stop = lane >= n - 1;
-  if (lane < n) {
-    r = rew[slot];
-    d = done[slot];
-    stop = stop || d != 0.f || ep_end[slot] != 0.f || slot == newest;
-  }
-  float disc = 1.f;
-  for (int m = 0; m < n - 1; ++m)
-    if (m < lane) disc *= gamma;
-  // lane n-1 always votes, so the mask is never empty
-  const unsigned long long mask = __ballot(stop);
-  const int last = __ffsll((long long)mask) - 1;
-  const float term = disc * r;
-  float acc = 0.f;
-  for (int m = 0; m <= last; ++m) acc += __shfl(term, m);
-  *R = acc;
-  const float de = 1.f - disc * (1.f - d);
-  *deff = __shfl(de, last);
-  return (idx + last) % cap;
-}
-
-// gather2 with n-step returns: same grid, index draw (key, counter,
-// ctr_add) and output layout as gather2_kernel; rew/done carry the
-// discounted n-step reward sum and the effective done, and XC rows B: hold
-// next_state of the window's LAST slot.  The loss kernels are unchanged:
-// gamma * (1 - done_eff) == gamma^M * (1 - done[last]).
-__global__ __launch_bounds__(256)
-void gather2n_kernel(const float* __restrict__ state,
-                     const float* __restrict__ act,
-                     const float* __restrict__ rew,
-                     const float* __restrict__ nstate,
-                     const float* __restrict__ done,
-                     const float* __restrict__ ep_end,
-                     const int64_t* __restrict__ size_dev,
-                     const int64_t* __restrict__ ptr_dev,
-                     const int64_t* __restrict__ ctr, int64_t ctr_add,
-                     uint64_t seed,
-                     float* __restrict__ xc,   // [2B, ldc]
-                     float* __restrict__ xc2,  // [B, ldc]
-                     float* __restrict__ orew, float* __restrict__ od,
-                     int B, int obs_dim, int act_dim, int ldc,
-                     int64_t cap, int n, float gamma) {
-  __shared__ int64_t s_last;
-  const int j = blockIdx.x;
-  const uint64_t size = (uint64_t)size_dev[0];
-  P4 r = philox_(seed, (uint64_t)(ctr[0] + ctr_add), (uint64_t)j);
-  uint64_t u = ((uint64_t)r.x << 32) | r.y;
-  int64_t idx = (int64_t)(u % (size ? size : 1));
-
-  if (threadIdx.x < 64) {
-    // size == 0: slot 0 counts as the newest, nothing past it is consumed
-    const int64_t newest = size ? (ptr_dev[0] + cap - 1) % cap : 0;
-    float R, de;
-    const int64_t last = nstep_walk_(rew, done, ep_end, idx, cap, newest, n,
-                                     gamma, &R, &de);
-    if (threadIdx.x == 0) {
-      s_last = last;
-      orew[j] = R;
-      od[j] = de;
-    }
-  }
-  const float* srow = state + idx * obs_dim;
-  const float* arow = act + idx * act_dim;
-  for (int c = threadIdx.x; c < obs_dim; c += blockDim.x) {
-    float s = srow[c];
-    xc[(int64_t)j * ldc + c] = s;           // s -> XC rows :B
-    xc2[(int64_t)j * ldc + c] = s;          // s -> XC2
-  }
-  for (int c = threadIdx.x; c < act_dim; c += blockDim.x)
-    xc[(int64_t)j * ldc + obs_dim + c] = arow[c];  // a -> XC rows :B
-  __syncthreads();
-  const float* nrow = nstate + s_last * obs_dim;
-  for (int c = threadIdx.x; c < obs_dim; c += blockDim.x)
-    xc[(int64_t)(B + j) * ldc + c] = nrow[c];  // ns[last] -> XC rows B:
-}
-
-// ---------------------------------------------------------------------------
-// Prioritized replay: fan-out-64 sum tree (buffer/replay.py::per_layout is
-// the layout, ::draw and ::_update_priorities_ref the executable definitions)
-// ---------------------------------------------------------------------------
-
-constexpr int PER_MAXL = 8;
-
-// Level k (0 = root, L = leaves) holds n[k] nodes at tree + off[k], padded
-// with zeros to a multiple of 64 so a wave always loads 64 in-bounds children.
-struct PerLay {
-  int L;
-  int64_t off[PER_MAXL];
-  int64_t n[PER_MAXL];
-};
-
-inline PerLay per_layout(int64_t cap, int64_t* total) {
-  PerLay lay;
-  int L = 1;
-  for (int64_t span = 64; span < cap; span *= 64) ++L;
-  TORCH_CHECK(cap >= 1 && L < PER_MAXL, "per: unsupported ring capacity");
-  lay.L = L;
-  lay.n[L] = cap;
-  for (int k = L - 1; k >= 0; --k) lay.n[k] = (lay.n[k + 1] + 63) / 64;
-  int64_t o = 0;
-  for (int k = 0; k <= L; ++k) {
-    lay.off[k] = o;
-    o += (lay.n[k] + 63) / 64 * 64;
-  }
-  for (int k = L + 1; k < PER_MAXL; ++k) lay.off[k] = lay.n[k] = 0;
-  *total = o;
-  return lay;
-}
-
-// Sum-tree descent for one target u — same code as
-// tac_kernels.hip::per_descend, duplicated to keep both translation units
-// self-contained.  Run by ONE full wave: per level, lane l loads child l of
-// the current node, a Hillis-Steele __shfl_up scan forms the inclusive
-// prefix P, and a ballot picks the first lane with P > u and c > 0 (the
-// scan is not monotone in floating point, so a zero child must not win);
-// if u rounded past the end, the last lane with c > 0; lane 0 in an empty
-// tree.  One dependent load per level.  All lanes return the same values.
-DEVINL int64_t per_descend_(const float* __restrict__ tree,
-                            const PerLay& lay, float u, float* prob) {
-  const int lane = threadIdx.x & 63;
-  int64_t node = 0;
-  float leaf = 0.f;
-  for (int k = 1; k <= lay.L; ++k) {
-    const float c = tree[lay.off[k] + node * 64 + lane];
-    float P = c;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const float t = __shfl_up(P, off);
-      if (lane >= off) P += t;
-    }
-    const bool pos = c > 0.f;
-    const unsigned long long hit = __ballot(pos && P > u);
-    const unsigned long long any = __ballot(pos);
-    const int pick = hit ? __ffsll((long long)hit) - 1
-                         : (any ? 63 - __clzll((long long)any) : 0);
-    const float Pp = __shfl(P, pick), cp = __shfl(c, pick);
-    u = fmaxf(u - (Pp - cp), 0.f);
-    node = node * 64 + pick;
-    leaf = cp;
-  }
-  const float root = tree[lay.off[0]];
-  *prob = root == 0.f ? 1.f : leaf / root;
-  return node;
-}
-
-// Stratified target of batch position j: u = (j + u01) * (root / B) with
-// u01 = (r.x >> 8) * 2^-24 from the Philox draw gather2 already makes.
-DEVINL float per_target_(const float* __restrict__ tree, const PerLay& lay,
-                         uint32_t rx, int j, int B) {
-#pragma clang fp contract(off)
-  const float u01 = (float)(rx >> 8) * 5.9604644775390625e-8f;
-  const float seg = tree[lay.off[0]] / (float)B;
-  return ((float)j + u01) * seg;
-}
-
-// gather2 drawing from the sum tree: same grid, output layout and Philox
-// keying as gather2_kernel.  Wave 0 descends and hands the slot to the
-// block through LDS; for n > 1 it then walks the n-step window from that
-// slot exactly as gather2n_kernel does.  Also writes the drawn slot, its
-// probability leaf / root and (tests only, when u_out is given) the target.
-__global__ __launch_bounds__(256)
-void gather2p_kernel(const float* __restrict__ state,
-                     const float* __restrict__ act,
-                     const float* __restrict__ rew,
-                     const float* __restrict__ nstate,
-                     const float* __restrict__ done,
-                     const float* __restrict__ ep_end,
-                     const int64_t* __restrict__ size_dev,
-                     const int64_t* __restrict__ ptr_dev,
-                     const float* __restrict__ tree, PerLay lay,
-                     const int64_t* __restrict__ ctr, int64_t ctr_add,
-                     uint64_t seed,
-                     float* __restrict__ xc,   // [2B, ldc]
-                     float* __restrict__ xc2,  // [B, ldc]
-                     float* __restrict__ orew, float* __restrict__ od,
-                     int64_t* __restrict__ idx_out,
-                     float* __restrict__ prob_out, float* __restrict__ u_out,
-                     int B, int obs_dim, int act_dim, int ldc,
-                     int64_t cap, int n, float gamma) {
-  __shared__ int64_t s_idx, s_last;
-  const int j = blockIdx.x;
-  if (threadIdx.x < 64) {
-    P4 r = philox_(seed, (uint64_t)(ctr[0] + ctr_add), (uint64_t)j);
-    const float u = per_target_(tree, lay, r.x, j, B);
-    float prob;
-    int64_t idx = per_descend_(tree, lay, u, &prob);
-    // a consistent tree never leads past the ring; keep the copies in
-    // bounds whatever the tree holds
-    idx = idx < cap ? idx : cap - 1;
-    int64_t last = idx;
-    float R, de;
-    if (n > 1) {
-      const int64_t size = size_dev[0];
-      const int64_t newest = size ? (ptr_dev[0] + cap - 1) % cap : 0;
-      last = nstep_walk_(rew, done, ep_end, idx, cap, newest, n, gamma, &R,
-                         &de);
-    } else {
-      R = rew[idx];
-      de = done[idx];
-    }
-    if (threadIdx.x == 0) {
-      s_idx = idx;
-      s_last = last;
-      orew[j] = R;
-      od[j] = de;
-      idx_out[j] = idx;
-      prob_out[j] = prob;
-      if (u_out) u_out[j] = u;
-    }
-  }
-  __syncthreads();
-  const int64_t idx = s_idx;
-  const float* srow = state + idx * obs_dim;
-  const float* nrow = nstate + s_last * obs_dim;
-  const float* arow = act + idx * act_dim;
-  for (int c = threadIdx.x; c < obs_dim; c += blockDim.x) {
-    float s = srow[c];
-    xc[(int64_t)j * ldc + c] = s;           // s -> XC rows :B
-    xc2[(int64_t)j * ldc + c] = s;          // s -> XC2
-    xc[(int64_t)(B + j) * ldc + c] = nrow[c];  // ns[last] -> XC rows B:
-  }
-  for (int c = threadIdx.x; c < act_dim; c += blockDim.x)
-    xc[(int64_t)j * ldc + obs_dim + c] = arow[c];  // a -> XC rows :B
-}
 
 constexpr int PER_THREADS = 1024;   // 16 waves: 16 nodes per load round trip
 
@@ -1992,11 +1685,9 @@ void tg_fwd2_kernel(const float* __restrict__ hl,  // [R, 2A]: mu | log_std
   if (a < A) {
     const int64_t i = (int64_t)b * A + a;
     // philox noise: one draw per element (use lane of the quad)
-    P4 r = philox_(seed ^ 0x517cc1b727220a95ull,
-                   (uint64_t)(ctr[0] + ctr_add), (uint64_t)i);
-    float u0 = (r.x + 1.f) * 2.3283064365386963e-10f;
-    float u1 = (r.y + 1.f) * 2.3283064365386963e-10f;
-    float eps = sqrtf(-2.f * logf(u0)) * __cosf(6.283185307179586f * u1);
+    Philox4 r = philox4(seed ^ 0x517cc1b727220a95ull,
+                        (uint64_t)(ctr[0] + ctr_add), (uint64_t)i);
+    float eps = philox_normal(r.x, r.y);
 
     float m = hl[(int64_t)b * 2 * A + a];
     float ls = fminf(fmaxf(hl[(int64_t)b * 2 * A + A + a], lo), hi);
@@ -2034,10 +1725,8 @@ void tg_eps_kernel(float* __restrict__ eps_out, uint64_t ctr_val,
   const int a = threadIdx.x;
   if (a >= A) return;
   const int64_t i = (int64_t)b * A + a;
-  P4 r = philox_(seed ^ 0x517cc1b727220a95ull, ctr_val, (uint64_t)i);
-  float u0 = (r.x + 1.f) * 2.3283064365386963e-10f;
-  float u1 = (r.y + 1.f) * 2.3283064365386963e-10f;
-  eps_out[i] = sqrtf(-2.f * logf(u0)) * __cosf(6.283185307179586f * u1);
+  Philox4 r = philox4(seed ^ 0x517cc1b727220a95ull, ctr_val, (uint64_t)i);
+  eps_out[i] = philox_normal(r.x, r.y);
 }
 
 // backward over rows :B of the stacked forward; dpi read from the dxc
@@ -2303,10 +1992,8 @@ void act_kernel(ActArgs a, ActPinned hp) {
       ls += wl[k] * h;
     }
     ls = fminf(fmaxf(ls, a.lo), a.hi);
-    P4 r = philox_(a.seed ^ 0x517cc1b727220a95ull, ctr_s, (uint64_t)tid);
-    float u0 = (r.x + 1.f) * 2.3283064365386963e-10f;
-    float u1 = (r.y + 1.f) * 2.3283064365386963e-10f;
-    float eps = sqrtf(-2.f * logf(u0)) * __cosf(6.283185307179586f * u1);
+    Philox4 r = philox4(a.seed ^ 0x517cc1b727220a95ull, ctr_s, (uint64_t)tid);
+    float eps = philox_normal(r.x, r.y);
     float act = tanhf(mu + expf(ls) * eps) * a.act_limit;
     a.action[tid] = act;
     if (hp.out_host) hp.out_host[tid] = act;
@@ -2417,11 +2104,10 @@ void act_batch_kernel(ActArgs a, int N, int ldx, int deterministic,
       for (int r = 0; r < ACTB_R; ++r) {
         if (r < nrow) {
           const float l = fminf(fmaxf(ls[r], a.lo), a.hi);
-          P4 p = philox_(a.seed ^ 0x2545f4914f6cdd1dull, ctr_val,
-                         (uint64_t)(row0 + r) * (uint64_t)a.A + (uint64_t)tid);
-          float u0 = (p.x + 1.f) * 2.3283064365386963e-10f;
-          float u1 = (p.y + 1.f) * 2.3283064365386963e-10f;
-          float eps = sqrtf(-2.f * logf(u0)) * __cosf(6.283185307179586f * u1);
+          Philox4 p = philox4(
+              a.seed ^ 0x2545f4914f6cdd1dull, ctr_val,
+              (uint64_t)(row0 + r) * (uint64_t)a.A + (uint64_t)tid);
+          float eps = philox_normal(p.x, p.y);
           a.action[(int64_t)(row0 + r) * a.A + tid] =
               tanhf(mu[r] + expf(l) * eps) * a.act_limit;
         }
@@ -3073,22 +2759,29 @@ void transpose_multi(std::vector<torch::Tensor> ws,
                      stream(), t);
 }
 
+// Replay gather writing straight into the concat-layout batch buffers
+// XC [2B, ldc] / XC2 [B, ldc]: one launch, keyed on ctr[0] + ctr_add so a
+// reader can run ahead of the counter bump.  gather2n carries n-step
+// returns, gather2p draws from the sum tree (either n).
+inline ConcatSink concat_sink(const torch::Tensor& xc,
+                              const torch::Tensor& xc2, int64_t B,
+                              const torch::Tensor& state) {
+  return {xc.data_ptr<float>(), xc2.data_ptr<float>(), (int)B,
+          (int)xc.size(1), (int)state.size(1)};
+}
+
 void gather2(torch::Tensor state, torch::Tensor act, torch::Tensor rew,
              torch::Tensor nstate, torch::Tensor done,
              torch::Tensor size_dev, torch::Tensor ctr, int64_t seed,
              torch::Tensor xc, torch::Tensor xc2, torch::Tensor orew,
              torch::Tensor od, int64_t B, int64_t ctr_add) {
-  const int obs_dim = (int)state.size(1);
-  const int act_dim = (int)act.size(1);
-  int threads = std::min<int>(256, std::max(64, ((obs_dim + 63) / 64) * 64));
-  hipLaunchKernelGGL(gather2_kernel, dim3((int)B), dim3(threads), 0, stream(),
-                     state.data_ptr<float>(), act.data_ptr<float>(),
-                     rew.data_ptr<float>(), nstate.data_ptr<float>(),
-                     done.data_ptr<float>(), size_dev.data_ptr<int64_t>(),
-                     ctr.data_ptr<int64_t>(), ctr_add, (uint64_t)seed,
-                     xc.data_ptr<float>(), xc2.data_ptr<float>(),
-                     orew.data_ptr<float>(), od.data_ptr<float>(),
-                     (int)B, obs_dim, act_dim, (int)xc.size(1));
+  const RingArgs ring{state, act, rew, nstate, done, nullptr, size_dev,
+                      nullptr, ctr};
+  const BatchArgs out{xc, xc2, nullptr, orew, od, nullptr, nullptr, nullptr};
+  gather_gate("gather2", ring, 1, B, out);
+  launch_gather<Draw::Uniform>(stream(), ring, nullptr, PerLay{}, ctr_add,
+                               seed, 1, 1.0, concat_sink(xc, xc2, B, state),
+                               out, B);
 }
 
 void gather2n(torch::Tensor state, torch::Tensor act, torch::Tensor rew,
@@ -3097,53 +2790,13 @@ void gather2n(torch::Tensor state, torch::Tensor act, torch::Tensor rew,
               torch::Tensor ctr, int64_t seed, int64_t n, double gamma,
               torch::Tensor xc, torch::Tensor xc2, torch::Tensor orew,
               torch::Tensor od, int64_t B, int64_t ctr_add) {
-  const int obs_dim = (int)state.size(1);
-  const int act_dim = (int)act.size(1);
-  const int64_t cap = state.size(0);
-  TORCH_CHECK(n >= 1 && n <= 64, "n_step must be in 1..64");
-  for (const torch::Tensor& t : {state, act, rew, nstate, done, ep_end, xc,
-                                 xc2, orew, od})
-    TORCH_CHECK(t.is_cuda() && t.is_contiguous() &&
-                t.dtype() == torch::kFloat32,
-                "gather2n: tensors must be contiguous fp32 device tensors");
-  TORCH_CHECK(cap >= 1 && rew.numel() == cap && done.numel() == cap &&
-              ep_end.numel() == cap && nstate.size(0) == cap &&
-              nstate.size(1) == obs_dim && act.size(0) == cap,
-              "gather2n: ring fields must share one capacity");
-  TORCH_CHECK(ptr_dev.is_cuda() && ptr_dev.dtype() == torch::kInt64 &&
-              ptr_dev.numel() == 1 && size_dev.is_cuda() &&
-              size_dev.dtype() == torch::kInt64 && size_dev.numel() == 1,
-              "gather2n: size_dev / ptr_dev must be int64 [1] device tensors");
-  TORCH_CHECK(B >= 1 && xc.size(0) >= 2 * B && xc2.size(0) >= B &&
-              xc.size(1) >= obs_dim + act_dim && xc2.size(1) == xc.size(1) &&
-              orew.numel() >= B && od.numel() >= B,
-              "gather2n: batch buffers too small");
-  int threads = std::min<int>(256, std::max(64, ((obs_dim + 63) / 64) * 64));
-  hipLaunchKernelGGL(gather2n_kernel, dim3((int)B), dim3(threads), 0,
-                     stream(),
-                     state.data_ptr<float>(), act.data_ptr<float>(),
-                     rew.data_ptr<float>(), nstate.data_ptr<float>(),
-                     done.data_ptr<float>(), ep_end.data_ptr<float>(),
-                     size_dev.data_ptr<int64_t>(),
-                     ptr_dev.data_ptr<int64_t>(),
-                     ctr.data_ptr<int64_t>(), ctr_add, (uint64_t)seed,
-                     xc.data_ptr<float>(), xc2.data_ptr<float>(),
-                     orew.data_ptr<float>(), od.data_ptr<float>(),
-                     (int)B, obs_dim, act_dim, (int)xc.size(1), cap, (int)n,
-                     (float)gamma);
-}
-
-// The sum tree of a ring with `cap` slots; checks the flat tensor against
-// the layout every per_* launch indexes it with.
-PerLay per_tree_layout(const torch::Tensor& tree, int64_t cap,
-                       const char* who) {
-  int64_t total = 0;
-  PerLay lay = per_layout(cap, &total);
-  TORCH_CHECK(tree.is_cuda() && tree.is_contiguous() &&
-              tree.dtype() == torch::kFloat32 && tree.numel() == total,
-              who, ": tree must be a contiguous fp32 device tensor of ",
-              total, " elements for a ring of ", cap);
-  return lay;
+  const RingArgs ring{state, act, rew, nstate, done, &ep_end, size_dev,
+                      &ptr_dev, ctr};
+  const BatchArgs out{xc, xc2, nullptr, orew, od, nullptr, nullptr, nullptr};
+  gather_gate("gather2n", ring, n, B, out);
+  launch_gather<Draw::UniformN>(stream(), ring, nullptr, PerLay{}, ctr_add,
+                                seed, n, gamma,
+                                concat_sink(xc, xc2, B, state), out, B);
 }
 
 void gather2p(torch::Tensor state, torch::Tensor act, torch::Tensor rew,
@@ -3154,49 +2807,14 @@ void gather2p(torch::Tensor state, torch::Tensor act, torch::Tensor rew,
               torch::Tensor orew, torch::Tensor od, torch::Tensor idx_out,
               torch::Tensor prob_out, c10::optional<torch::Tensor> u_out,
               int64_t B, int64_t ctr_add) {
-  const int obs_dim = (int)state.size(1);
-  const int act_dim = (int)act.size(1);
-  const int64_t cap = state.size(0);
-  TORCH_CHECK(n >= 1 && n <= 64, "n_step must be in 1..64");
-  for (const torch::Tensor& t : {state, act, rew, nstate, done, ep_end, xc,
-                                 xc2, orew, od, prob_out})
-    TORCH_CHECK(t.is_cuda() && t.is_contiguous() &&
-                t.dtype() == torch::kFloat32,
-                "gather2p: tensors must be contiguous fp32 device tensors");
-  TORCH_CHECK(cap >= 1 && rew.numel() == cap && done.numel() == cap &&
-              ep_end.numel() == cap && nstate.size(0) == cap &&
-              nstate.size(1) == obs_dim && act.size(0) == cap,
-              "gather2p: ring fields must share one capacity");
-  TORCH_CHECK(ptr_dev.is_cuda() && ptr_dev.dtype() == torch::kInt64 &&
-              ptr_dev.numel() == 1 && size_dev.is_cuda() &&
-              size_dev.dtype() == torch::kInt64 && size_dev.numel() == 1,
-              "gather2p: size_dev / ptr_dev must be int64 [1] device tensors");
-  TORCH_CHECK(B >= 1 && xc.size(0) >= 2 * B && xc2.size(0) >= B &&
-              xc.size(1) >= obs_dim + act_dim && xc2.size(1) == xc.size(1) &&
-              orew.numel() >= B && od.numel() >= B && prob_out.numel() >= B &&
-              idx_out.is_cuda() && idx_out.is_contiguous() &&
-              idx_out.dtype() == torch::kInt64 && idx_out.numel() >= B,
-              "gather2p: batch buffers too small");
-  TORCH_CHECK(!u_out.has_value() ||
-              (u_out->is_cuda() && u_out->is_contiguous() &&
-               u_out->dtype() == torch::kFloat32 && u_out->numel() >= B),
-              "gather2p: bad u_out");
-  PerLay lay = per_tree_layout(tree, cap, "gather2p");
-  int threads = std::min<int>(256, std::max(64, ((obs_dim + 63) / 64) * 64));
-  hipLaunchKernelGGL(gather2p_kernel, dim3((int)B), dim3(threads), 0,
-                     stream(),
-                     state.data_ptr<float>(), act.data_ptr<float>(),
-                     rew.data_ptr<float>(), nstate.data_ptr<float>(),
-                     done.data_ptr<float>(), ep_end.data_ptr<float>(),
-                     size_dev.data_ptr<int64_t>(),
-                     ptr_dev.data_ptr<int64_t>(), tree.data_ptr<float>(),
-                     lay, ctr.data_ptr<int64_t>(), ctr_add, (uint64_t)seed,
-                     xc.data_ptr<float>(), xc2.data_ptr<float>(),
-                     orew.data_ptr<float>(), od.data_ptr<float>(),
-                     idx_out.data_ptr<int64_t>(), prob_out.data_ptr<float>(),
-                     u_out.has_value() ? u_out->data_ptr<float>() : nullptr,
-                     (int)B, obs_dim, act_dim, (int)xc.size(1), cap, (int)n,
-                     (float)gamma);
+  const RingArgs ring{state, act, rew, nstate, done, &ep_end, size_dev,
+                      &ptr_dev, ctr};
+  const BatchArgs out{xc, xc2, nullptr, orew, od, &idx_out, &prob_out,
+                      u_out.has_value() ? &*u_out : nullptr};
+  gather_gate("gather2p", ring, n, B, out);
+  const PerLay lay = per_tree_layout(tree, state.size(0), "gather2p");
+  launch_gather<Draw::Tree>(stream(), ring, &tree, lay, ctr_add, seed, n,
+                            gamma, concat_sink(xc, xc2, B, state), out, B);
 }
 
 void per_update(torch::Tensor tree, int64_t cap, torch::Tensor idx,

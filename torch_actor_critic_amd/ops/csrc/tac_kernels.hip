@@ -27,60 +27,20 @@
 #include <cmath>
 #include <vector>
 
-#define DEVINL __device__ __forceinline__
+#include "replay_draw.h"
 
 namespace {
 
+using namespace replay;
+
 constexpr int WAVE = 64;
 
-// ---------------------------------------------------------------------------
-// Philox4x32-10 counter-based RNG (device-side, graph-replay-safe)
-// ---------------------------------------------------------------------------
-
-struct Philox4 {
-  uint32_t x, y, z, w;
-};
-
-DEVINL uint32_t mulhilo(uint32_t a, uint32_t b, uint32_t* hi) {
-  uint64_t p = (uint64_t)a * (uint64_t)b;
-  *hi = (uint32_t)(p >> 32);
-  return (uint32_t)p;
-}
-
-DEVINL Philox4 philox4(uint64_t seed, uint64_t ctr_hi, uint64_t ctr_lo) {
-  uint32_t c0 = (uint32_t)ctr_lo, c1 = (uint32_t)(ctr_lo >> 32);
-  uint32_t c2 = (uint32_t)ctr_hi, c3 = (uint32_t)(ctr_hi >> 32);
-  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-  const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
-  const uint32_t W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    uint32_t hi0, hi1;
-    uint32_t lo0 = mulhilo(M0, c0, &hi0);
-    uint32_t lo1 = mulhilo(M1, c2, &hi1);
-    uint32_t n0 = hi1 ^ c1 ^ k0;
-    uint32_t n1 = lo1;
-    uint32_t n2 = hi0 ^ c3 ^ k1;
-    uint32_t n3 = lo0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += W0; k1 += W1;
-  }
-  return {c0, c1, c2, c3};
-}
-
-// Debug/test helper: the four raw output words of subsequences
-// clo0 .. clo0 + n - 1, so the generator itself can be held against a
-// host implementation (tests/kernel_refs.py::philox4x32).
+// Debug/test helper: the raw Philox words of subsequences clo0 ..
+// clo0 + n - 1 as this translation unit compiled the generator.
 __global__ __launch_bounds__(256)
 void philox_words_kernel(int64_t* __restrict__ out, uint64_t seed,
                          uint64_t chi, uint64_t clo0, int64_t n) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  Philox4 r = philox4(seed, chi, clo0 + (uint64_t)i);
-  out[4 * i + 0] = (int64_t)r.x;
-  out[4 * i + 1] = (int64_t)r.y;
-  out[4 * i + 2] = (int64_t)r.z;
-  out[4 * i + 3] = (int64_t)r.w;
+  philox_words_row(out, seed, chi, clo0, n);
 }
 
 // ---------------------------------------------------------------------------
@@ -695,284 +655,6 @@ void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
 }
 
 // ---------------------------------------------------------------------------
-// Replay sample + gather (Philox, with replacement)
-// ---------------------------------------------------------------------------
-
-// grid.x = B (one block per sampled row); all threads of a block copy the
-// row's fields.  idx_j = philox(seed, ctr, j) % size.
-__global__ __launch_bounds__(256)
-void replay_gather_kernel(const float* __restrict__ state,
-                          const float* __restrict__ act,
-                          const float* __restrict__ rew,
-                          const float* __restrict__ nstate,
-                          const float* __restrict__ done,
-                          const int64_t* __restrict__ size_dev,
-                          const int64_t* __restrict__ ctr,
-                          uint64_t seed,
-                          float* __restrict__ os, float* __restrict__ oa,
-                          float* __restrict__ orew, float* __restrict__ ons,
-                          float* __restrict__ od,
-                          int obs_dim, int act_dim) {
-  const int j = blockIdx.x;
-  const uint64_t size = (uint64_t)size_dev[0];
-  Philox4 r = philox4(seed, (uint64_t)ctr[0], (uint64_t)j);
-  // 64-bit uniform to keep modulo bias negligible at 1e6 sizes
-  uint64_t u = ((uint64_t)r.x << 32) | r.y;
-  int64_t idx = (int64_t)(u % (size ? size : 1));
-
-  const float* srow = state + (int64_t)idx * obs_dim;
-  const float* nrow = nstate + (int64_t)idx * obs_dim;
-  float* osr = os + (int64_t)j * obs_dim;
-  float* onr = ons + (int64_t)j * obs_dim;
-  for (int c = threadIdx.x; c < obs_dim; c += blockDim.x) {
-    osr[c] = srow[c];
-    onr[c] = nrow[c];
-  }
-  const float* arow = act + (int64_t)idx * act_dim;
-  float* oar = oa + (int64_t)j * act_dim;
-  for (int c = threadIdx.x; c < act_dim; c += blockDim.x) oar[c] = arow[c];
-  if (threadIdx.x == 0) {
-    orew[j] = rew[idx];
-    od[j] = done[idx];
-  }
-}
-
-// ---------------------------------------------------------------------------
-// N-step replay sample + gather (buffer/replay.py::sample_at is the
-// executable definition of the window semantics)
-// ---------------------------------------------------------------------------
-
-// N-step window walk for one sampled slot, run by ONE full wave (all 64
-// lanes active, n <= 64).  Lane m < n loads (rew, done, episode_end) of
-// slot (idx+m) % cap and forms its own gamma^m by repeated multiply; a
-// wave64 ballot finds the first lane whose slot closes the window
-// (terminal, episode boundary, newest slot, or m == n-1), so the n slots
-// cost one global-load latency instead of a chain of n dependent loads.
-// R = sum_{m<M} gamma^m rew[m] is added in ascending m (the reference
-// order), deff = 1 - gamma^(M-1) * (1 - done[last]); contraction is off so
-// every product is rounded before it is added, as in the reference.
-// Returns the last slot of the window; all lanes get the same values.
-DEVINL int64_t nstep_walk(const float* __restrict__ rew,
-                          const float* __restrict__ done,
-                          const float* __restrict__ ep_end, int64_t idx,
-                          int64_t cap, int64_t newest, int n, float gamma,
-                          float* R, float* deff) {
-#pragma clang fp contract(off)
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int64_t slot = (idx + lane) % cap;
-  float r = 0.f, d = 0.f;
-  bool stop = lane >= n - 1;
-  if (lane < n) {
-    r = rew[slot];
-    d = done[slot];
-    stop = stop || d != 0.f || ep_end[slot] != 0.f || slot == newest;
-  }
-  float disc = 1.f;
-  for (int m = 0; m < n - 1; ++m)
-    if (m < lane) disc *= gamma;
-  // lane n-1 always votes, so the mask is never empty
-  const unsigned long long mask = __ballot(stop);
-  const int last = __ffsll((long long)mask) - 1;
-  const float term = disc * r;
-  float acc = 0.f;
-  for (int m = 0; m <= last; ++m) acc += __shfl(term, m);
-  *R = acc;
-  const float de = 1.f - disc * (1.f - d);
-  *deff = __shfl(de, last);
-  return (idx + last) % cap;
-}
-
-// Same grid and index draw as replay_gather_kernel (same key, counter and
-// block -> row map, so for one counter value both pick the same slots).
-// Wave 0 walks the window and hands the last slot to the block through
-// LDS; state/action rows are copied from slot idx, next_state from the
-// last slot.  cap is the ring capacity; with size == 0 slot 0 counts as
-// the newest slot, so nothing beyond it is consumed.
-__global__ __launch_bounds__(256)
-void replay_gather_n_kernel(const float* __restrict__ state,
-                            const float* __restrict__ act,
-                            const float* __restrict__ rew,
-                            const float* __restrict__ nstate,
-                            const float* __restrict__ done,
-                            const float* __restrict__ ep_end,
-                            const int64_t* __restrict__ size_dev,
-                            const int64_t* __restrict__ ptr_dev,
-                            const int64_t* __restrict__ ctr,
-                            uint64_t seed,
-                            float* __restrict__ os, float* __restrict__ oa,
-                            float* __restrict__ orew, float* __restrict__ ons,
-                            float* __restrict__ od,
-                            int obs_dim, int act_dim, int64_t cap, int n,
-                            float gamma) {
-  __shared__ int64_t s_last;
-  const int j = blockIdx.x;
-  const uint64_t size = (uint64_t)size_dev[0];
-  Philox4 r = philox4(seed, (uint64_t)ctr[0], (uint64_t)j);
-  uint64_t u = ((uint64_t)r.x << 32) | r.y;
-  int64_t idx = (int64_t)(u % (size ? size : 1));
-
-  if (threadIdx.x < WAVE) {
-    const int64_t newest = size ? (ptr_dev[0] + cap - 1) % cap : 0;
-    float R, de;
-    const int64_t last = nstep_walk(rew, done, ep_end, idx, cap, newest, n,
-                                    gamma, &R, &de);
-    if (threadIdx.x == 0) {
-      s_last = last;
-      orew[j] = R;
-      od[j] = de;
-    }
-  }
-  const float* srow = state + (int64_t)idx * obs_dim;
-  float* osr = os + (int64_t)j * obs_dim;
-  for (int c = threadIdx.x; c < obs_dim; c += blockDim.x) osr[c] = srow[c];
-  const float* arow = act + (int64_t)idx * act_dim;
-  float* oar = oa + (int64_t)j * act_dim;
-  for (int c = threadIdx.x; c < act_dim; c += blockDim.x) oar[c] = arow[c];
-  __syncthreads();
-  const float* nrow = nstate + s_last * obs_dim;
-  float* onr = ons + (int64_t)j * obs_dim;
-  for (int c = threadIdx.x; c < obs_dim; c += blockDim.x) onr[c] = nrow[c];
-}
-
-// ---------------------------------------------------------------------------
-// Prioritized replay sample + gather from the fan-out-64 sum tree
-// (buffer/replay.py::per_layout is the layout, ::draw the definition)
-// ---------------------------------------------------------------------------
-
-constexpr int PER_MAXL = 8;
-
-// Level k (0 = root, L = leaves) holds n[k] nodes at tree + off[k], padded
-// with zeros to a multiple of 64 so a wave always loads 64 in-bounds children.
-struct PerLay {
-  int L;
-  int64_t off[PER_MAXL];
-  int64_t n[PER_MAXL];
-};
-
-// Sum-tree descent for one target u, run by ONE full wave.  Per level,
-// lane l loads child l of the current node (one coalesced 256-byte load —
-// the fan-out is the wave width), a Hillis-Steele __shfl_up scan forms the
-// inclusive prefix P and a ballot picks the first lane with P > u and
-// c > 0.  The c > 0 guard is required: the scan is not monotone in
-// floating point, so without it a zero child could win.  If u rounded past
-// the end the last lane with c > 0 is taken, lane 0 in an empty tree.  The
-// remainder u - (P[pick] - c[pick]), clamped at 0, goes down one level:
-// L dependent loads per sample.  prob = leaf / root (1 for an empty tree).
-// All lanes return the same values.
-DEVINL int64_t per_descend(const float* __restrict__ tree, const PerLay& lay,
-                           float u, float* prob) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  int64_t node = 0;
-  float leaf = 0.f;
-  for (int k = 1; k <= lay.L; ++k) {
-    const float c = tree[lay.off[k] + node * 64 + lane];
-    float P = c;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const float t = __shfl_up(P, off);
-      if (lane >= off) P += t;
-    }
-    const bool pos = c > 0.f;
-    const unsigned long long hit = __ballot(pos && P > u);
-    const unsigned long long any = __ballot(pos);
-    const int pick = hit ? __ffsll((long long)hit) - 1
-                         : (any ? 63 - __clzll((long long)any) : 0);
-    const float Pp = __shfl(P, pick), cp = __shfl(c, pick);
-    u = fmaxf(u - (Pp - cp), 0.f);
-    node = node * 64 + pick;
-    leaf = cp;
-  }
-  const float root = tree[lay.off[0]];
-  *prob = root == 0.f ? 1.f : leaf / root;
-  return node;
-}
-
-// Stratified target of batch position j: u = (j + u01) * (root / B) with
-// u01 = (r.x >> 8) * 2^-24 from the Philox draw replay_gather_kernel makes.
-DEVINL float per_target(const float* __restrict__ tree, const PerLay& lay,
-                        uint32_t rx, int j, int B) {
-#pragma clang fp contract(off)
-  const float u01 = (float)(rx >> 8) * 5.9604644775390625e-8f;
-  const float seg = tree[lay.off[0]] / (float)B;
-  return ((float)j + u01) * seg;
-}
-
-// Same grid and Philox keying as replay_gather_kernel.  Wave 0 descends the
-// tree and hands the slot to the block through LDS; for n > 1 it then walks
-// the n-step window from that slot as replay_gather_n_kernel does.  Writes
-// the drawn slot, its probability and (when given) the target u.  With
-// os == nullptr nothing is gathered (the standalone per_sample binding).
-__global__ __launch_bounds__(256)
-void replay_gather_p_kernel(const float* __restrict__ state,
-                            const float* __restrict__ act,
-                            const float* __restrict__ rew,
-                            const float* __restrict__ nstate,
-                            const float* __restrict__ done,
-                            const float* __restrict__ ep_end,
-                            const int64_t* __restrict__ size_dev,
-                            const int64_t* __restrict__ ptr_dev,
-                            const float* __restrict__ tree, PerLay lay,
-                            const int64_t* __restrict__ ctr, uint64_t seed,
-                            float* __restrict__ os, float* __restrict__ oa,
-                            float* __restrict__ orew, float* __restrict__ ons,
-                            float* __restrict__ od,
-                            int64_t* __restrict__ idx_out,
-                            float* __restrict__ prob_out,
-                            float* __restrict__ u_out,
-                            int B, int obs_dim, int act_dim, int64_t cap,
-                            int n, float gamma) {
-  __shared__ int64_t s_idx, s_last;
-  const int j = blockIdx.x;
-  const bool gather = os != nullptr;
-  if (threadIdx.x < WAVE) {
-    Philox4 r = philox4(seed, (uint64_t)ctr[0], (uint64_t)j);
-    const float u = per_target(tree, lay, r.x, j, B);
-    float prob;
-    int64_t idx = per_descend(tree, lay, u, &prob);
-    // a consistent tree never leads past the ring; keep the copies in
-    // bounds whatever the tree holds
-    idx = idx < cap ? idx : cap - 1;
-    int64_t last = idx;
-    if (gather) {
-      float R, de;
-      if (n > 1) {
-        const int64_t size = size_dev[0];
-        const int64_t newest = size ? (ptr_dev[0] + cap - 1) % cap : 0;
-        last = nstep_walk(rew, done, ep_end, idx, cap, newest, n, gamma, &R,
-                          &de);
-      } else {
-        R = rew[idx];
-        de = done[idx];
-      }
-      if (threadIdx.x == 0) {
-        orew[j] = R;
-        od[j] = de;
-      }
-    }
-    if (threadIdx.x == 0) {
-      s_idx = idx;
-      s_last = last;
-      idx_out[j] = idx;
-      prob_out[j] = prob;
-      if (u_out) u_out[j] = u;
-    }
-  }
-  if (!gather) return;
-  __syncthreads();
-  const float* srow = state + s_idx * obs_dim;
-  const float* nrow = nstate + s_last * obs_dim;
-  float* osr = os + (int64_t)j * obs_dim;
-  float* onr = ons + (int64_t)j * obs_dim;
-  for (int c = threadIdx.x; c < obs_dim; c += blockDim.x) {
-    osr[c] = srow[c];
-    onr[c] = nrow[c];
-  }
-  const float* arow = act + s_idx * act_dim;
-  float* oar = oa + (int64_t)j * act_dim;
-  for (int c = threadIdx.x; c < act_dim; c += blockDim.x) oar[c] = arow[c];
-}
-
-// ---------------------------------------------------------------------------
 // Visual replay gather: ONE kernel draws the Philox index and copies
 // features / frames (with u8 -> f32 dequantization) / actions / rewards
 // / done into the static batch — replaces ~18 aten index/copy/decode
@@ -1005,8 +687,7 @@ void visual_gather_kernel(const float* __restrict__ feat,
   const int nslice = gridDim.y;
   const uint64_t size = (uint64_t)size_dev[0];
   Philox4 r = philox4(seed, (uint64_t)ctr[0], (uint64_t)j);
-  uint64_t u = ((uint64_t)r.x << 32) | r.y;
-  const int64_t idx = (int64_t)(u % (size ? size : 1));
+  const int64_t idx = uniform_slot(r, size);
 
   if (slice == 0) {
     for (int c = threadIdx.x; c < feat_dim; c += blockDim.x) {
@@ -1138,8 +819,7 @@ void visual_gather_shift_kernel(const float* __restrict__ feat,
   const int nslice = gridDim.y;
   const uint64_t size = (uint64_t)size_dev[0];
   Philox4 r = philox4(seed, (uint64_t)ctr[0], (uint64_t)j);
-  uint64_t u = ((uint64_t)r.x << 32) | r.y;
-  const int64_t idx = (int64_t)(u % (size ? size : 1));
+  const int64_t idx = uniform_slot(r, size);
   const uint32_t span = 2u * (uint32_t)pad + 1u;
   const int dy0 = (int)((r.z >> 16) % span) - pad;
   const int dx0 = (int)((r.z & 0xffffu) % span) - pad;
@@ -1225,8 +905,7 @@ void visual_gather_n_kernel(const float* __restrict__ feat,
   const int nslice = gridDim.y;
   const uint64_t size = (uint64_t)size_dev[0];
   Philox4 r = philox4(seed, (uint64_t)ctr[0], (uint64_t)j);
-  uint64_t u = ((uint64_t)r.x << 32) | r.y;
-  const int64_t idx = (int64_t)(u % (size ? size : 1));
+  const int64_t idx = uniform_slot(r, size);
   const uint32_t span = 2u * (uint32_t)pad + 1u;
   const int dy0 = (int)((r.z >> 16) % span) - pad;
   const int dx0 = (int)((r.z & 0xffffu) % span) - pad;
@@ -1234,8 +913,7 @@ void visual_gather_n_kernel(const float* __restrict__ feat,
   const int dx1 = (int)((r.w & 0xffffu) % span) - pad;
 
   if (threadIdx.x < WAVE) {
-    // with size == 0 slot 0 counts as the newest: the window is slot 0
-    const int64_t newest = size ? (ptr_dev[0] + cap - 1) % cap : 0;
+    const int64_t newest = newest_slot(size, ptr_dev, cap);
     float R, de;
     const int64_t last = nstep_walk(rew, done, ep_end, idx, cap, newest, n,
                                     gamma, &R, &de);
@@ -1610,28 +1288,30 @@ void adam_step_(torch::Tensor p, torch::Tensor g, torch::Tensor m,
                      (float)b2, (float)eps, (float)wd);
 }
 
+// The flat batch tensors as the gather's sink (after gather_gate).
+inline FlatSink flat_sink(const torch::Tensor& os, const torch::Tensor& oa,
+                          const torch::Tensor& ons) {
+  return {os.data_ptr<float>(), oa.data_ptr<float>(), ons.data_ptr<float>(),
+          (int)os.size(1), (int)oa.size(1)};
+}
+
+// The samplers below bump the counter and draw on the new value; the gate
+// runs first, so a refused call leaves the counter alone.
 void replay_sample_into(torch::Tensor state, torch::Tensor act,
                         torch::Tensor rew, torch::Tensor nstate,
                         torch::Tensor done, torch::Tensor size_dev,
                         torch::Tensor ctr, int64_t seed,
                         torch::Tensor os, torch::Tensor oa, torch::Tensor orew,
                         torch::Tensor ons, torch::Tensor od) {
-  CHECK_IN(state); CHECK_IN(os);
-  const int B = os.size(0);
-  const int obs_dim = state.size(1);
-  const int act_dim = act.size(1);
-  auto s = cur_stream();
-  hipLaunchKernelGGL(bump_counter_kernel, dim3(1), dim3(1), 0, s,
+  const RingArgs ring{state, act, rew, nstate, done, nullptr, size_dev,
+                      nullptr, ctr};
+  const BatchArgs out{os, oa, &ons, orew, od, nullptr, nullptr, nullptr};
+  const int64_t B = os.dim() ? os.size(0) : 0;
+  gather_gate("replay_sample_into", ring, 1, B, out);
+  hipLaunchKernelGGL(bump_counter_kernel, dim3(1), dim3(1), 0, cur_stream(),
                      ctr.data_ptr<int64_t>());
-  int threads = std::min(256, std::max(64, ((obs_dim + 63) / 64) * 64));
-  hipLaunchKernelGGL(replay_gather_kernel, dim3(B), dim3(threads), 0, s,
-                     state.data_ptr<float>(), act.data_ptr<float>(),
-                     rew.data_ptr<float>(), nstate.data_ptr<float>(),
-                     done.data_ptr<float>(), size_dev.data_ptr<int64_t>(),
-                     ctr.data_ptr<int64_t>(), (uint64_t)seed,
-                     os.data_ptr<float>(), oa.data_ptr<float>(),
-                     orew.data_ptr<float>(), ons.data_ptr<float>(),
-                     od.data_ptr<float>(), obs_dim, act_dim);
+  launch_gather<Draw::Uniform>(cur_stream(), ring, nullptr, PerLay{}, 0, seed,
+                               1, 1.0, flat_sink(os, oa, ons), out, B);
 }
 
 // n-step variant (n > 1): ep_end is the ring's episode-boundary field and
@@ -1646,61 +1326,16 @@ void replay_sample_into_n(torch::Tensor state, torch::Tensor act,
                           torch::Tensor os, torch::Tensor oa,
                           torch::Tensor orew, torch::Tensor ons,
                           torch::Tensor od) {
-  CHECK_IN(state); CHECK_IN(act); CHECK_IN(rew); CHECK_IN(nstate);
-  CHECK_IN(done); CHECK_IN(ep_end);
-  CHECK_IN(os); CHECK_IN(oa); CHECK_IN(orew); CHECK_IN(ons); CHECK_IN(od);
-  TORCH_CHECK(n >= 1 && n <= 64, "n_step must be in 1..64");
-  const int64_t cap = state.size(0);
-  TORCH_CHECK(cap >= 1 && rew.numel() == cap && done.numel() == cap &&
-              ep_end.numel() == cap && nstate.size(0) == cap &&
-              act.size(0) == cap, "ring fields must share one capacity");
-  TORCH_CHECK(ptr_dev.is_cuda() && ptr_dev.dtype() == torch::kInt64 &&
-              ptr_dev.numel() == 1 && size_dev.is_cuda() &&
-              size_dev.dtype() == torch::kInt64 && size_dev.numel() == 1,
-              "size_dev / ptr_dev must be int64 [1] device tensors");
-  const int B = os.size(0);
-  const int obs_dim = state.size(1);
-  const int act_dim = act.size(1);
-  TORCH_CHECK(os.size(1) == obs_dim && ons.size(1) == obs_dim &&
-              ons.size(0) == B && oa.size(0) == B && oa.size(1) == act_dim &&
-              orew.numel() == B && od.numel() == B, "batch shape mismatch");
-  auto s = cur_stream();
-  hipLaunchKernelGGL(bump_counter_kernel, dim3(1), dim3(1), 0, s,
+  const RingArgs ring{state, act, rew, nstate, done, &ep_end, size_dev,
+                      &ptr_dev, ctr};
+  const BatchArgs out{os, oa, &ons, orew, od, nullptr, nullptr, nullptr};
+  const int64_t B = os.dim() ? os.size(0) : 0;
+  gather_gate("replay_sample_into_n", ring, n, B, out);
+  hipLaunchKernelGGL(bump_counter_kernel, dim3(1), dim3(1), 0, cur_stream(),
                      ctr.data_ptr<int64_t>());
-  int threads = std::min(256, std::max(64, ((obs_dim + 63) / 64) * 64));
-  hipLaunchKernelGGL(replay_gather_n_kernel, dim3(B), dim3(threads), 0, s,
-                     state.data_ptr<float>(), act.data_ptr<float>(),
-                     rew.data_ptr<float>(), nstate.data_ptr<float>(),
-                     done.data_ptr<float>(), ep_end.data_ptr<float>(),
-                     size_dev.data_ptr<int64_t>(),
-                     ptr_dev.data_ptr<int64_t>(),
-                     ctr.data_ptr<int64_t>(), (uint64_t)seed,
-                     os.data_ptr<float>(), oa.data_ptr<float>(),
-                     orew.data_ptr<float>(), ons.data_ptr<float>(),
-                     od.data_ptr<float>(), obs_dim, act_dim, cap, (int)n,
-                     (float)gamma);
-}
-
-// Layout of the sum tree over `cap` leaves, checked against the flat tensor.
-PerLay per_tree_layout(const torch::Tensor& tree, int64_t cap) {
-  PerLay lay;
-  int L = 1;
-  for (int64_t span = 64; span < cap; span *= 64) ++L;
-  TORCH_CHECK(cap >= 1 && L < PER_MAXL, "per: unsupported ring capacity");
-  lay.L = L;
-  lay.n[L] = cap;
-  for (int k = L - 1; k >= 0; --k) lay.n[k] = (lay.n[k + 1] + 63) / 64;
-  int64_t total = 0;
-  for (int k = 0; k <= L; ++k) {
-    lay.off[k] = total;
-    total += (lay.n[k] + 63) / 64 * 64;
-  }
-  for (int k = L + 1; k < PER_MAXL; ++k) lay.off[k] = lay.n[k] = 0;
-  TORCH_CHECK(tree.is_cuda() && tree.is_contiguous() &&
-              tree.dtype() == torch::kFloat32 && tree.numel() == total,
-              "per: tree must be a contiguous fp32 device tensor of ", total,
-              " elements for a ring of ", cap);
-  return lay;
+  launch_gather<Draw::UniformN>(cur_stream(), ring, nullptr, PerLay{}, 0,
+                                seed, n, gamma, flat_sink(os, oa, ons), out,
+                                B);
 }
 
 // Prioritized variant: slots come from the sum tree `tree` of the ring
@@ -1717,45 +1352,17 @@ void replay_sample_into_p(torch::Tensor state, torch::Tensor act,
                           torch::Tensor orew, torch::Tensor ons,
                           torch::Tensor od, torch::Tensor oidx,
                           torch::Tensor oprob) {
-  CHECK_IN(state); CHECK_IN(act); CHECK_IN(rew); CHECK_IN(nstate);
-  CHECK_IN(done); CHECK_IN(ep_end);
-  CHECK_IN(os); CHECK_IN(oa); CHECK_IN(orew); CHECK_IN(ons); CHECK_IN(od);
-  CHECK_IN(oprob);
-  TORCH_CHECK(n >= 1 && n <= 64, "n_step must be in 1..64");
-  const int64_t cap = state.size(0);
-  TORCH_CHECK(cap >= 1 && rew.numel() == cap && done.numel() == cap &&
-              ep_end.numel() == cap && nstate.size(0) == cap &&
-              act.size(0) == cap, "ring fields must share one capacity");
-  TORCH_CHECK(ptr_dev.is_cuda() && ptr_dev.dtype() == torch::kInt64 &&
-              ptr_dev.numel() == 1 && size_dev.is_cuda() &&
-              size_dev.dtype() == torch::kInt64 && size_dev.numel() == 1,
-              "size_dev / ptr_dev must be int64 [1] device tensors");
-  const int B = os.size(0);
-  const int obs_dim = state.size(1);
-  const int act_dim = act.size(1);
-  TORCH_CHECK(B >= 1 && os.size(1) == obs_dim && ons.size(1) == obs_dim &&
-              ons.size(0) == B && oa.size(0) == B && oa.size(1) == act_dim &&
-              orew.numel() == B && od.numel() == B && oprob.numel() == B &&
-              oidx.is_cuda() && oidx.is_contiguous() &&
-              oidx.dtype() == torch::kInt64 && oidx.numel() == B,
-              "batch shape mismatch");
-  PerLay lay = per_tree_layout(tree, cap);
-  auto s = cur_stream();
-  hipLaunchKernelGGL(bump_counter_kernel, dim3(1), dim3(1), 0, s,
+  const RingArgs ring{state, act, rew, nstate, done, &ep_end, size_dev,
+                      &ptr_dev, ctr};
+  const BatchArgs out{os, oa, &ons, orew, od, &oidx, &oprob, nullptr};
+  const int64_t B = os.dim() ? os.size(0) : 0;
+  gather_gate("replay_sample_into_p", ring, n, B, out);
+  const PerLay lay =
+      per_tree_layout(tree, state.size(0), "replay_sample_into_p");
+  hipLaunchKernelGGL(bump_counter_kernel, dim3(1), dim3(1), 0, cur_stream(),
                      ctr.data_ptr<int64_t>());
-  int threads = std::min(256, std::max(64, ((obs_dim + 63) / 64) * 64));
-  hipLaunchKernelGGL(replay_gather_p_kernel, dim3(B), dim3(threads), 0, s,
-                     state.data_ptr<float>(), act.data_ptr<float>(),
-                     rew.data_ptr<float>(), nstate.data_ptr<float>(),
-                     done.data_ptr<float>(), ep_end.data_ptr<float>(),
-                     size_dev.data_ptr<int64_t>(),
-                     ptr_dev.data_ptr<int64_t>(), tree.data_ptr<float>(),
-                     lay, ctr.data_ptr<int64_t>(), (uint64_t)seed,
-                     os.data_ptr<float>(), oa.data_ptr<float>(),
-                     orew.data_ptr<float>(), ons.data_ptr<float>(),
-                     od.data_ptr<float>(), oidx.data_ptr<int64_t>(),
-                     oprob.data_ptr<float>(), (float*)nullptr, B, obs_dim,
-                     act_dim, cap, (int)n, (float)gamma);
+  launch_gather<Draw::Tree>(cur_stream(), ring, &tree, lay, 0, seed, n, gamma,
+                            flat_sink(os, oa, ons), out, B);
 }
 
 // The draw alone: (slot, probability, target u) for `batch` stratified
@@ -1763,25 +1370,27 @@ void replay_sample_into_p(torch::Tensor state, torch::Tensor act,
 std::vector<torch::Tensor> per_sample(torch::Tensor tree, int64_t cap,
                                       torch::Tensor ctr, int64_t seed,
                                       int64_t batch) {
-  PerLay lay = per_tree_layout(tree, cap);
+  PerLay lay = per_tree_layout(tree, cap, "per_sample");
   TORCH_CHECK(batch >= 1 && batch < (int64_t(1) << 31), "bad batch size");
   TORCH_CHECK(ctr.is_cuda() && ctr.dtype() == torch::kInt64 &&
               ctr.numel() == 1, "ctr must be an int64 [1] device tensor");
   auto oidx = torch::empty({batch}, tree.options().dtype(torch::kInt64));
   auto oprob = torch::empty({batch}, tree.options());
   auto ou = torch::empty({batch}, tree.options());
-  auto s = cur_stream();
-  hipLaunchKernelGGL(bump_counter_kernel, dim3(1), dim3(1), 0, s,
+  hipLaunchKernelGGL(bump_counter_kernel, dim3(1), dim3(1), 0, cur_stream(),
                      ctr.data_ptr<int64_t>());
   const float* nf = nullptr;
   const int64_t* ni = nullptr;
   float* nout = nullptr;
-  hipLaunchKernelGGL(replay_gather_p_kernel, dim3((int)batch), dim3(64), 0, s,
-                     nf, nf, nf, nf, nf, nf, ni, ni, tree.data_ptr<float>(),
-                     lay, ctr.data_ptr<int64_t>(), (uint64_t)seed, nout, nout,
-                     nout, nout, nout, oidx.data_ptr<int64_t>(),
-                     oprob.data_ptr<float>(), ou.data_ptr<float>(),
-                     (int)batch, 0, 0, cap, 1, 1.0f);
+  hipLaunchKernelGGL((gather_kernel<Draw::Tree, FlatSink>),
+                     dim3((int)batch), dim3(64), 0, cur_stream(),
+                     nf, nf, nf, nf, nf, ni, ctr.data_ptr<int64_t>(),
+                     int64_t(0), (uint64_t)seed,
+                     FlatSink{nullptr, nullptr, nullptr, 0, 0}, nout, nout,
+                     (int)batch, 0, 0, nf, ni, cap, 1, 1.0f,
+                     TreeArgs{tree.data_ptr<float>(), lay,
+                              oidx.data_ptr<int64_t>(),
+                              oprob.data_ptr<float>(), ou.data_ptr<float>()});
   return {oidx, oprob, ou};
 }
 
