@@ -2,14 +2,28 @@
 
 Replaces the autograd-recorded update (112 kernels/update, 75% of GPU
 time in scalar-staged GEMMs — profiles/r01_baseline_update_profile.md)
-with an explicit kernel schedule of 24 launches at batch 64 (26 with the
-three folds below switched off, 22 with the Adam fold forced on) built
-from the multi-problem MFMA kernels in ops/csrc/fused.hip:
+with an explicit kernel schedule of 22 launches at batch 64 (21 with the
+pi-loss fold switched on, 24 with the q-loss fold switched off, 26 with
+the bump and rank-1 folds off as well, 20 with the Adam fold forced on)
+built from the multi-problem MFMA kernels in ops/csrc/fused.hip:
 
  * one Philox counter bump covers the replay draw AND the policy noise;
    it has no launch of its own: gather2/tg_fwd2 key on ctr+1 and the
-   single-block qloss2, which runs after both, commits ctr and both Adam
-   step counters (TAC_AMD_BUMP_FOLD=0 restores the bump3 launch);
+   launch that computes the q-loss, which runs after both, commits ctr
+   and both Adam step counters (TAC_AMD_BUMP_FOLD=0 restores the bump3
+   launch);
+ * where the small-shape bf16 GEMM runs (batch <= 128, hidden <= 256)
+   neither loss has a launch of its own.  The critic phase's masked
+   dgrad of the last hidden layer computes the Bellman backup and dq per
+   staged row, forms dq (x) w_last in registers (so the K=1 dgrad launch
+   goes too), writes dq and that outer product for the wgrad, and its
+   block (0, 0, 0) reduces the loss and commits the counters
+   (mgemm_r1_qloss; TAC_AMD_QLOSS_FOLD=0 restores qloss2 + the K=1
+   launch; needs two hidden layers and the unweighted loss).  The policy
+   phase's rank-1 dgrad does the same with the pi-loss (mgemm_r1_piloss;
+   off by default, TAC_AMD_PILOSS_FOLD=1 switches it on).  Both are
+   decided when a phase is recorded and give the unfolded schedule's
+   bits;
  * at world=1 a phase's heterogeneous wgrad launch can apply Adam
    (+polyak, +W^T refresh) itself, replacing the adam_t launch.  By
    default (TAC_AMD_WGRAD_ADAM=auto) it does so where the launch splits
@@ -276,6 +290,26 @@ class FusedSACEngine:
             _log.info("engine: rank-1 dgrad operand off (last-layer W^T "
                       "row is not 16-byte aligned); keeping the K=1 launch")
             self._r1_dgrad = False
+        # Loss kernels folded into the GEMM that follows them: the critic
+        # phase's qloss2 + K=1 dgrad go into the masked dgrad
+        # (mgemm_r1_qloss), the policy phase's piloss2 into mgemm_r1
+        # (mgemm_r1_piloss).  The flags only ask; each phase decides when
+        # it is recorded (_fold_q / _fold_pi), because the folded form
+        # exists for the small-shape bf16 kernel alone and both the
+        # compute dtype and mgemm_small_mode can change after construction.
+        self._qloss_fold_req = (
+            os.environ.get("TAC_AMD_QLOSS_FOLD", "1") != "0")
+        # The q fold measured +3.9 % on the headline and ships on; the pi
+        # fold measured +1.7 % on --mode updates but inside the run-to-run
+        # spread on the headline, so it stays behind TAC_AMD_PILOSS_FOLD=1
+        # (OPTIMIZATION_LOG.md, "Loss folds").
+        self._piloss_fold_req = (
+            os.environ.get("TAC_AMD_PILOSS_FOLD", "0") == "1")
+        self._qloss_fold = False
+        self._piloss_fold = False
+        # host-only predicate, no launch: bound here so that it does not
+        # count among the launcher calls made through self.ext
+        self._fold_ok = self.ext.mgemm_r1_fold_ok
         self._s2 = torch.cuda.Stream()
         self._fork_evs = [torch.cuda.Event() for _ in range(12)]
         self._join_evs = [torch.cuda.Event() for _ in range(4)]
@@ -379,6 +413,31 @@ class FusedSACEngine:
         else:
             self.ext.mwgrad_het(*cols)
         self._wjobs = []
+
+    def _fold_q(self) -> bool:
+        """Does this recording fold qloss2 and the K=1 dgrad into the
+        masked dgrad of the layer below?  Needs a GEMM behind the K=1
+        launch (two hidden layers), the unweighted loss, the phase-wide
+        wgrad launch (it reads dq and the outer product after the folded
+        launch wrote them) and the small-shape kernel."""
+        nL = len(self.c_w)
+        ok = (self._qloss_fold_req and nL >= 3 and not self.per
+              and not self._loss_fuse and self._wgrad_batch
+              and all(self.cwt[z][nL - 1].data_ptr() % 16 == 0
+                      and self.dc[z][nL - 2].data_ptr() % 16 == 0
+                      for z in range(2))
+              and self._fold_ok(self.B, self.c_w[nL - 2]))
+        self._qloss_fold = bool(ok)
+        return self._qloss_fold
+
+    def _fold_pi(self) -> bool:
+        """Does this recording fold piloss2 into the rank-1 dgrad GEMM?"""
+        nL = len(self.c_w)
+        ok = (self._piloss_fold_req and self._r1_dgrad
+              and not self._loss_fuse
+              and self._fold_ok(self.B, self.c_w[nL - 2]))
+        self._piloss_fold = bool(ok)
+        return self._piloss_fold
 
     def _mg(self, xs, ws, bs, ys, masks, M, N, K, lda, ldy, relu,
             xs2=None, ws2=None, masks2=None, K2=0, x_off=0, x2_off=0,
@@ -540,15 +599,19 @@ class FusedSACEngine:
         buf = self.buffer
         per = ((self.pprob, buf._size_dev, buf._beta_dev, self.td)
                if self.per else ())
-        ext.qloss2(q[0], q[1], qt[0], qt[1], self.logp[B:], self.rew,
-                   self.done, self.alpha_dev, self.alpha_host,
-                   self.loss_q_acc, self.dq[0], self.dq[1], B,
-                   self.sac.gamma, self.sac.reward_scale,
-                   self.cwt[0][nL - 1] if fuse else None,
-                   self.cwt[1][nL - 1] if fuse else None,
-                   self.dc[0][nL - 2] if fuse else None,
-                   self.dc[1][nL - 2] if fuse else None,
-                   self.c_w[nL - 2] if fuse else 0, *bump, *per)
+        # folded: no loss launch and no K=1 launch here — the masked
+        # dgrad below computes dq, the outer product and the loss itself
+        qfold = self._fold_q()
+        if not qfold:
+            ext.qloss2(q[0], q[1], qt[0], qt[1], self.logp[B:], self.rew,
+                       self.done, self.alpha_dev, self.alpha_host,
+                       self.loss_q_acc, self.dq[0], self.dq[1], B,
+                       self.sac.gamma, self.sac.reward_scale,
+                       self.cwt[0][nL - 1] if fuse else None,
+                       self.cwt[1][nL - 1] if fuse else None,
+                       self.dc[0][nL - 2] if fuse else None,
+                       self.dc[1][nL - 2] if fuse else None,
+                       self.c_w[nL - 2] if fuse else 0, *bump, *per)
         if self.per:
             # new priorities from this batch's TD errors, ahead of
             # everything that can precede the next gather
@@ -574,8 +637,19 @@ class FusedSACEngine:
                         (self.c_w[i - 1] if i > 0 else OC),
                         self.c_w[i], ldx, xoff)
             if i > 0:
-                if i == nL - 1 and fuse:
-                    pass  # dy2 already produced by the fused loss kernel
+                if i == nL - 1 and (fuse or qfold):
+                    pass  # dy2 comes from the loss kernel / the next GEMM
+                elif i == nL - 2 and qfold:
+                    ext.mgemm_r1_qloss(
+                        q[0], q[1], qt[0], qt[1], self.logp[B:], self.rew,
+                        self.done, self.alpha_dev, self.alpha_host,
+                        self.loss_q_acc, self.dq[0], self.dq[1],
+                        self.sac.gamma, self.sac.reward_scale, *bump,
+                        [self.cwt[z][nL - 1] for z in range(2)],
+                        [self.cwt[z][i] for z in range(2)],
+                        [self.dc[z][i - 1] for z in range(2)], masks,
+                        [self.dc[z][i] for z in range(2)],
+                        B, self.c_w[i - 1], self.c_w[i], self.c_w[i - 1])
                 else:
                     self._mg(d, [self.cwt[z][i] for z in range(2)],
                              [None, None],
@@ -607,14 +681,26 @@ class FusedSACEngine:
         nL = len(self.c_w)
         qp = [self.p_act[z][nL - 1] for z in range(2)]
         fuse = self._loss_fuse
-        ext.piloss2(qp[0], qp[1], self.logp[:B], self.alpha_dev,
+        # folded: the rank-1 GEMM below computes dqp and the loss itself
+        pfold = self._fold_pi()
+        if not pfold:
+            ext.piloss2(qp[0], qp[1], self.logp[:B], self.alpha_dev,
+                        self.alpha_host, self.loss_pi_acc, self.mean_logp,
+                        self.dqp[0], self.dqp[1], B,
+                        self.cwt[0][nL - 1] if fuse else None,
+                        self.cwt[1][nL - 1] if fuse else None,
+                        self.dcp[0][nL - 2] if fuse else None,
+                        self.dcp[1][nL - 2] if fuse else None,
+                        self.c_w[nL - 2] if fuse else 0)
+
+        def r1_gemm(cols, rows, ws, ys, masks, M, N, K, ldy):
+            if pfold:
+                ext.mgemm_r1_piloss(
+                    qp[0], qp[1], self.logp[:B], self.alpha_dev,
                     self.alpha_host, self.loss_pi_acc, self.mean_logp,
-                    self.dqp[0], self.dqp[1], B,
-                    self.cwt[0][nL - 1] if fuse else None,
-                    self.cwt[1][nL - 1] if fuse else None,
-                    self.dcp[0][nL - 2] if fuse else None,
-                    self.dcp[1][nL - 2] if fuse else None,
-                    self.c_w[nL - 2] if fuse else 0)
+                    cols[0], cols[1], rows, ws, ys, masks, M, N, K, ldy)
+            else:
+                ext.mgemm_r1(cols, rows, ws, ys, masks, M, N, K, ldy)
 
         # critic dgrad chain only (frozen critic).  The last layer's
         # dgrad is the outer product dqp (x) w_last (K=1): with r1 it is
@@ -632,11 +718,10 @@ class FusedSACEngine:
                       [self.cwt[z][nL - 1] for z in range(2)])
                 continue
             if r1 is not None:
-                ext.mgemm_r1(r1[0], r1[1],
-                             [self.cwt[z][i] for z in range(2)],
-                             [self.dcp[z][i - 1] for z in range(2)], masks,
-                             B, self.c_w[i - 1], self.c_w[i],
-                             self.c_w[i - 1])
+                r1_gemm(r1[0], r1[1],
+                        [self.cwt[z][i] for z in range(2)],
+                        [self.dcp[z][i - 1] for z in range(2)], masks,
+                        B, self.c_w[i - 1], self.c_w[i], self.c_w[i - 1])
                 r1 = None
             else:
                 self._mg(d, [self.cwt[z][i] for z in range(2)],
@@ -649,9 +734,9 @@ class FusedSACEngine:
         # them on read (measured faster than the serial two-pass sum2)
         masks0 = [self.p_act[z][0] for z in range(2)]
         if r1 is not None:   # single hidden layer: layer 0 consumes it
-            ext.mgemm_r1(r1[0], r1[1], [self.cwt[z][0] for z in range(2)],
-                         [self.dxc, self.dxc2], masks0, B, OC, self.c_w[0],
-                         self.OCp)
+            r1_gemm(r1[0], r1[1], [self.cwt[z][0] for z in range(2)],
+                    [self.dxc, self.dxc2], masks0, B, OC, self.c_w[0],
+                    self.OCp)
         else:
             self._mg(d, [self.cwt[z][0] for z in range(2)], [None, None],
                      [self.dxc, self.dxc2], masks0,

@@ -570,6 +570,111 @@ void mgemm_combine_kernel(MGemm g, int split, bool relu) {
 }
 
 // ---------------------------------------------------------------------------
+// SAC loss rows and their block reduction, shared by the single-block loss
+// kernels (qloss2 / piloss2) and by the small-shape GEMM that forms a loss
+// gradient column while staging (mgemm_small_kernel's LF modes).  The roundings
+// are spelled out the way the loss kernels have always compiled (one fused
+// multiply-add per row, nothing else contracted), so every kernel that
+// inlines these gives the same bits whatever surrounds the call.
+// ---------------------------------------------------------------------------
+
+struct QRow { float g1, g2, sq; };   // dq1, dq2, e1^2 + e2^2
+
+DEVINL QRow qloss_row(float q1, float q2, float q1t, float q2t, float lpn,
+                      float rew, float done, float alpha, float gamma,
+                      float scale, int B) {
+#pragma clang fp contract(off)
+  const float soft = __builtin_fmaf(-alpha, lpn, fminf(q1t, q2t));
+  const float backup = scale * rew + gamma * (1.f - done) * soft;
+  const float e1 = q1 - backup, e2 = q2 - backup;
+  QRow r;
+  r.sq = e1 * e1 + e2 * e2;
+  r.g1 = 2.f * e1 / B;
+  r.g2 = 2.f * e2 / B;
+  return r;
+}
+
+struct PiRow { float g1, g2, s; };   // dqp1, dqp2, alpha logp - min(q1, q2)
+
+DEVINL PiRow piloss_row(float q1, float q2, float lp, float alpha, int B) {
+#pragma clang fp contract(off)
+  PiRow r;
+  r.s = __builtin_fmaf(alpha, lp, -fminf(q1, q2));
+  float g1, g2;
+  if (q1 < q2)      { g1 = -1.f; g2 = 0.f; }
+  else if (q2 < q1) { g1 = 0.f;  g2 = -1.f; }
+  else              { g1 = -0.5f; g2 = -0.5f; }
+  r.g1 = g1 / B;
+  r.g2 = g2 / B;
+  return r;
+}
+
+struct QIn {
+  const float* q1; const float* q2; const float* q1t; const float* q2t;
+  const float* lpn; const float* rew; const float* done;
+};
+
+// one row's loss inputs (the pi-loss uses q1, q2 and lpn = logp)
+struct QVals { float q1, q2, q1t, q2t, lpn, rew, done; };
+
+DEVINL QVals qvals_load(const QIn& in, int i) {
+  return QVals{in.q1[i], in.q2[i], in.q1t[i], in.q2t[i], in.lpn[i],
+               in.rew[i], in.done[i]};
+}
+
+// strided per-thread sums over the whole batch: load(i) gives row i's
+// inputs (from memory, or from registers filled ahead of time), each(i,
+// row) sees every row
+template <class L, class F>
+DEVINL float qloss_rows(L&& load, float alpha, float gamma, float scale,
+                        int B, F&& each) {
+#pragma clang fp contract(off)
+  float acc = 0.f;
+  for (int i = threadIdx.x; i < B; i += blockDim.x) {
+    const QVals v = load(i);
+    const QRow r = qloss_row(v.q1, v.q2, v.q1t, v.q2t, v.lpn, v.rew, v.done,
+                             alpha, gamma, scale, B);
+    acc += r.sq;
+    each(i, r);
+  }
+  return acc;
+}
+
+template <class L, class F>
+DEVINL void piloss_rows(float (&acc)[2], L&& load, float alpha, int B,
+                        F&& each) {
+#pragma clang fp contract(off)
+  acc[0] = 0.f;
+  acc[1] = 0.f;
+  for (int i = threadIdx.x; i < B; i += blockDim.x) {
+    const QVals v = load(i);
+    const PiRow r = piloss_row(v.q1, v.q2, v.lpn, alpha, B);
+    acc[0] += r.s;
+    acc[1] += v.lpn;
+    each(i, r);
+  }
+}
+
+// block means of N per-thread sums (256 threads): 64-lane shuffle, one
+// partial per wave through red[n][0..3], summed in wave order, / B.  Holds
+// a barrier, so the whole block calls it.
+template <int N>
+DEVINL void loss_block_mean(float (&acc)[N], float (*red)[4], int B) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+    for (int n = 0; n < N; ++n) acc[n] += __shfl_down(acc[n], off);
+  if ((threadIdx.x & 63) == 0)
+#pragma unroll
+    for (int n = 0; n < N; ++n) red[n][threadIdx.x >> 6] = acc[n];
+  __syncthreads();
+#pragma unroll
+  for (int n = 0; n < N; ++n)
+    acc[n] = (red[n][0] + red[n][1] + red[n][2] + red[n][3]) / B;
+}
+
+// ---------------------------------------------------------------------------
 // Small-shape mgemm (bf16 compute, M <= 128, K <= 256, K2 <= 256): the
 // batch-64 update's GEMMs are latency-bound, not throughput-bound.  The
 // pipelined kernel above walks K in 128-wide steps with a dependent
@@ -603,7 +708,8 @@ DEVINL bool small_vec_ok(const float* src, const float* mask, int r0, int R,
 // clamped (valid) address and are zeroed by small_write.
 //  * vec:   4 lanes x float4 per row; R = 32 splits K over two row sets
 //  * !vec:  16 lanes x dword per row, rows rr + 16p
-template <int R, bool MASK, bool R1>
+// LF != 0 (computed rank-1 column, see LossFold): the caller fills ra.
+template <int R, bool MASK, bool R1, int LF = 0>
 DEVINL void small_load(float (&v)[R], float (&mk)[MASK ? R : 1],
                        float (&ra)[R / 16], bool vec,
                        const float* src, const float* mask,
@@ -616,7 +722,7 @@ DEVINL void small_load(float (&v)[R], float (&mk)[MASK ? R : 1],
     const int gr = r0 + ((tid >> 2) & (R - 1));
     const int kg = (tid >> 2) / R;
     const int c = tid & 3;
-    if constexpr (R1) ra[0] = r1c[gr];
+    if constexpr (R1 && LF == 0) ra[0] = r1c[gr];
     const float* base = R1 ? r1r : src + (int64_t)gr * ld;
     const float* mbase = MASK ? mask + (int64_t)gr * ld : nullptr;
 #pragma unroll
@@ -644,7 +750,7 @@ DEVINL void small_load(float (&v)[R], float (&mk)[MASK ? R : 1],
     for (int p = 0; p < R / 16; ++p) {
       const bool rows_in = r0 + 16 * p < bound;
       const int gr = min(r0 + rr + 16 * p, bound - 1);
-      if constexpr (R1) ra[p] = r1c[gr];
+      if constexpr (R1 && LF == 0) ra[p] = r1c[gr];
 #pragma unroll
       for (int q = 0; q < SKMAX / 16; ++q) {
         if (rows_in && q * 16 < K) {
@@ -713,11 +819,140 @@ DEVINL void small_write(__bf16* d, int S, const float (&v)[R],
   }
 }
 
-template <int TM, int TN, bool MASK, bool RELU, bool SUM2, bool R1>
+// A rank-1 column that the GEMM computes itself instead of reading it: the
+// SAC loss gradient dq_z (blockIdx.z = z, nz = 2) of each staged row, from
+// the inputs of the loss kernel this launch replaces.  LF = 1: pi-loss
+// (q1, q2, logp -> dqp_z, loss_acc, mean_logp), LF = 2: q-loss (all seven
+// inputs -> dq_z, loss_acc, the counter commit).  The blockIdx.y == 0
+// blocks also write their rows of dq_z, and under LF = 2 their rows of the
+// unmasked fp32 outer product dq_z (x) row_z — what the K=1 GEMM that used
+// to sit in front stored for the wgrad to read.  Block (0, 0, 0) alone runs
+// the loss kernel's full-batch reduction; no other block reads what it
+// writes.
+struct LossFold {
+  QIn in;                   // LF = 1 reads q1, q2 and lpn (= logp) only
+  const float* alpha_dev; float alpha_host;
+  float gamma, scale;
+  float* loss_acc;
+  float* mean_logp;         // LF = 1, may be null
+  float* dq[2];             // [M] each
+  float* outer[2];          // LF = 2: [M, K], 16-byte aligned
+  int64_t* bump[3];         // LF = 2, each may be null
+};
+
+// What block (0, 0, 0) reads for the reduction, loaded with the block's
+// other loads so the launch keeps its single memory round trip: the loss
+// inputs of row threadIdx.x (B <= 128 < blockDim.x, so the shared strided
+// loop visits no other row), and in thread 0 the accumulator and counters.
+struct FoldPre { QVals v; float loss0; int64_t c[3]; };
+
+template <int LF>
+DEVINL void fold_preload(FoldPre& pre, const LossFold& lf, int B) {
+  const int i = threadIdx.x;
+  if (i < B) {
+    pre.v.q1 = lf.in.q1[i];
+    pre.v.q2 = lf.in.q2[i];
+    pre.v.lpn = lf.in.lpn[i];
+    if constexpr (LF == 2) {
+      pre.v.q1t = lf.in.q1t[i];
+      pre.v.q2t = lf.in.q2t[i];
+      pre.v.rew = lf.in.rew[i];
+      pre.v.done = lf.in.done[i];
+    }
+  }
+  if (i == 0) {
+    pre.loss0 = lf.loss_acc[0];
+    if constexpr (LF == 2) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j)
+        if (lf.bump[j]) pre.c[j] = lf.bump[j][0];
+    }
+  }
+}
+
+// the loss kernel's reduction and scalar outputs, by one whole block
+template <int LF>
+DEVINL void fold_reduce(const FoldPre& pre, const LossFold& lf, float alpha,
+                        int B) {
+  __shared__ float red[2][4];
+  auto load = [&](int) { return pre.v; };
+  if constexpr (LF == 2) {
+    float acc[1];
+    acc[0] = qloss_rows(load, alpha, lf.gamma, lf.scale, B,
+                        [](int, const QRow&) {});
+    loss_block_mean<1>(acc, red, B);
+    if (threadIdx.x == 0) {
+      lf.loss_acc[0] = pre.loss0 + acc[0];
+#pragma unroll
+      for (int j = 0; j < 3; ++j)
+        if (lf.bump[j]) lf.bump[j][0] = pre.c[j] + 1;
+    }
+  } else {
+    float acc[2];
+    piloss_rows(acc, load, alpha, B, [](int, const PiRow&) {});
+    loss_block_mean<2>(acc, red, B);
+    if (threadIdx.x == 0) {
+      lf.loss_acc[0] = pre.loss0 + acc[0];
+      if (lf.mean_logp) lf.mean_logp[0] = acc[1];
+    }
+  }
+}
+
+// Store an R x K tile of the unmasked fp32 products ra * v at the element
+// map of small_write (same vec / r0 / bound / K); dst has row stride K.
+template <int R>
+DEVINL void fold_store_outer(float* dst, const float (&v)[R],
+                             const float (&ra)[R / 16], bool vec, int r0,
+                             int bound, int K) {
+  const int tid = threadIdx.x;
+  if (vec) {
+    constexpr int G = 64 / R;
+    constexpr int NQ = SKMAX / 16 / G;
+    const int gr = r0 + ((tid >> 2) & (R - 1));
+    const int kg = (tid >> 2) / R;
+    const int c = tid & 3;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const int col = ((q * G + kg) * 4 + c) * 4;
+      if (q * G * 16 < K && col < K) {   // K % 4 == 0: whole float4 inside
+        float4 f;
+        // + 0: a zero-accumulator MFMA never returns -0
+        f.x = ra[0] * v[q*4+0] + 0.f; f.y = ra[0] * v[q*4+1] + 0.f;
+        f.z = ra[0] * v[q*4+2] + 0.f; f.w = ra[0] * v[q*4+3] + 0.f;
+        *(float4*)(dst + (int64_t)gr * K + col) = f;
+      }
+    }
+  } else {
+    const int rr = tid >> 4;
+    const int cc = tid & 15;
+#pragma unroll
+    for (int p = 0; p < R / 16; ++p) {
+      const int gr = r0 + rr + 16 * p;
+#pragma unroll
+      for (int q = 0; q < SKMAX / 16; ++q) {
+        const int col = cc + 16 * q;
+        if (gr < bound && col < K)
+          dst[(int64_t)gr * K + col] = ra[p] * v[p*16+q] + 0.f;
+      }
+    }
+  }
+}
+
+DEVINL float bf16_round(float x) { return (float)(__bf16)x; }
+
+DEVINL const LossFold& fold_arg(const LossFold& lf) { return lf; }
+
+// LF != 0: masked R1 whose column is computed from loss inputs (1 pi, 2 q);
+// the LossFold then travels as a second by-value argument.  LF = 0 has no
+// such argument and compiles to what it was without the mode.
+template <int TM, int TN, bool MASK, bool RELU, bool SUM2, bool R1,
+          int LF = 0, class... Fold>
 __global__ __launch_bounds__(256)
-void mgemm_small_kernel(MGemm g) {
+void mgemm_small_kernel(MGemm g, Fold... fold) {
+  static_assert(sizeof...(Fold) == (LF != 0 ? 1 : 0), "one LossFold iff LF");
   static_assert((TM == 32 || TM == 64) && (TN == 32 || TN == 64), "tile");
   static_assert(!(SUM2 && R1), "R1 has no second operand");
+  static_assert(LF == 0 || (R1 && MASK), "a computed column is an R1 column");
   constexpr int WM = TM / 2, WN = TN / 2;      // per-wave sub-tile
   constexpr int MI = WM / 16, NI = WN / 16;
   constexpr int KT = SUM2 ? 2 * SKMAX : SKMAX;
@@ -752,8 +987,35 @@ void mgemm_small_kernel(MGemm g) {
   const bool veca = small_vec_ok(a_src, MASK ? p.mask : nullptr, bm0, TM,
                                  g.M, g.K, g.lda);
   const bool vecb = small_vec_ok(p.w, nullptr, bn0, TN, g.N, g.K, g.K);
-  small_load<TM, MASK, R1>(va, ma, ra, veca, p.x, p.mask, bm0, g.M, g.K,
-                           g.lda, p.r1_col, p.r1_row);
+  small_load<TM, MASK, R1, LF>(va, ma, ra, veca, p.x, p.mask, bm0, g.M, g.K,
+                               g.lda, p.r1_col, p.r1_row);
+  // computed column: this thread's staged rows (small_load's row map) load
+  // their loss inputs with everything else, ahead of the first wait
+  constexpr int NFR = LF ? TM / 16 : 1;
+  int frow[NFR];
+  float fin[NFR][LF == 2 ? 7 : 2];
+  float falpha = 0.f;
+  FoldPre fpre = {};
+  if constexpr (LF != 0) {
+    const LossFold& lf = fold_arg(fold...);
+    falpha = lf.alpha_dev ? lf.alpha_dev[0] : lf.alpha_host;
+#pragma unroll
+    for (int q = 0; q < NFR; ++q) {
+      frow[q] = veca ? bm0 + ((tid >> 2) & (TM - 1))
+                     : min(bm0 + (tid >> 4) + 16 * q, g.M - 1);
+      fin[q][0] = lf.in.q1[frow[q]];
+      fin[q][1] = lf.in.q2[frow[q]];
+      if constexpr (LF == 2) {
+        fin[q][2] = lf.in.q1t[frow[q]];
+        fin[q][3] = lf.in.q2t[frow[q]];
+        fin[q][4] = lf.in.lpn[frow[q]];
+        fin[q][5] = lf.in.rew[frow[q]];
+        fin[q][6] = lf.in.done[frow[q]];
+      }
+    }
+    if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0)
+      fold_preload<LF>(fpre, lf, g.M);
+  }
   small_load<TN, false, false>(vb, nomask, rb, vecb, p.w, nullptr, bn0, g.N,
                                g.K, g.K, nullptr, nullptr);
   float va2[SUM2 ? TM : 1], ma2[(SUM2 && MASK) ? TM : 1], vb2[SUM2 ? TN : 1];
@@ -768,6 +1030,40 @@ void mgemm_small_kernel(MGemm g) {
                                  g.N, g.K2, g.K2, nullptr, nullptr);
   }
 
+  if constexpr (LF != 0) {
+    const LossFold& lf = fold_arg(fold...);
+    const int z = blockIdx.z;
+    // lanes that own column 0 of a staged row write that row's dq_z
+    const bool wr = blockIdx.y == 0
+                    && (veca ? (tid & 3) == 0 && (tid >> 2) / TM == 0
+                             : (tid & 15) == 0);
+#pragma unroll
+    for (int q = 0; q < NFR; ++q) {
+      float col;
+      if constexpr (LF == 2) {
+        const QRow r = qloss_row(fin[q][0], fin[q][1], fin[q][2], fin[q][3],
+                                 fin[q][4], fin[q][5], fin[q][6], falpha,
+                                 lf.gamma, lf.scale, g.M);
+        col = z ? r.g2 : r.g1;
+      } else {
+        const PiRow r = piloss_row(fin[q][0], fin[q][1], 0.f, falpha, g.M);
+        col = z ? r.g2 : r.g1;
+      }
+      const bool row_in = veca ? q == 0 : bm0 + (tid >> 4) + 16 * q < g.M;
+      if (wr && row_in) lf.dq[z][frow[q]] = col;
+      // LF = 2 reproduces a K=1 bf16 MFMA launch (which stored
+      // bf16(dq) * bf16(w), exact in fp32) re-staged by the masked GEMM
+      ra[q] = LF == 2 ? bf16_round(col) : col;
+    }
+    if constexpr (LF == 2) {
+#pragma unroll
+      for (int e = 0; e < TM; ++e) va[e] = bf16_round(va[e]);
+      if (blockIdx.y == 0)
+        fold_store_outer<TM>(lf.outer[z], va, ra, veca, bm0, g.M, g.K);
+    }
+    if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0)
+      fold_reduce<LF>(fpre, lf, falpha, g.M);
+  }
   small_write<TM, MASK, R1>(xs, S, va, ma, ra, veca, bm0, g.M, g.K, Kp1);
   small_write<TN, false, false>(ws, S, vb, nomask, rb, vecb, bn0, g.N, g.K,
                                 Kp1);
@@ -1795,7 +2091,7 @@ void qloss2_kernel(const float* __restrict__ q1, const float* __restrict__ q2,
                    const int64_t* __restrict__ size_dev,
                    const float* __restrict__ beta_dev,
                    float* __restrict__ td) {
-  __shared__ float red[4];
+  __shared__ float red[1][4];
   __shared__ float dqs[2][LOSS_MAXB];
   const float alpha = alpha_dev ? alpha_dev[0] : alpha_host;
   const bool fuse = dy2_0 != nullptr;
@@ -1822,32 +2118,33 @@ void qloss2_kernel(const float* __restrict__ q1, const float* __restrict__ q2,
     wmax = fmaxf(fmaxf(redw[0], redw[1]), fmaxf(redw[2], redw[3]));
   }
   float acc = 0.f;
-  for (int i = threadIdx.x; i < B; i += blockDim.x) {
-    float backup = scale * rew[i] + gamma * (1.f - done[i]) *
-                       (fminf(q1t[i], q2t[i]) - alpha * logp_next[i]);
-    float e1 = q1[i] - backup, e2 = q2[i] - backup;
-    float g1, g2;
-    if constexpr (WEIGHTED) {
+  if constexpr (WEIGHTED) {
+    for (int i = threadIdx.x; i < B; i += blockDim.x) {
+      float backup = scale * rew[i] + gamma * (1.f - done[i]) *
+                         (fminf(q1t[i], q2t[i]) - alpha * logp_next[i]);
+      float e1 = q1[i] - backup, e2 = q2[i] - backup;
       const float w = powf(wsize * prob[i], nbeta) / wmax;
       acc += w * (e1 * e1 + e2 * e2);
-      g1 = 2.f * (w * e1) / B;
-      g2 = 2.f * (w * e2) / B;
+      const float g1 = 2.f * (w * e1) / B;
+      const float g2 = 2.f * (w * e2) / B;
       td[i] = 0.5f * (fabsf(e1) + fabsf(e2));
-    } else {
-      acc += e1 * e1 + e2 * e2;
-      g1 = 2.f * e1 / B;
-      g2 = 2.f * e2 / B;
+      dq1[i] = g1;
+      dq2[i] = g2;
+      if (fuse) { dqs[0][i] = g1; dqs[1][i] = g2; }
     }
-    dq1[i] = g1;
-    dq2[i] = g2;
-    if (fuse) { dqs[0][i] = g1; dqs[1][i] = g2; }
+  } else {
+    const QIn in{q1, q2, q1t, q2t, logp_next, rew, done};
+    auto load = [&](int i) { return qvals_load(in, i); };
+    acc = qloss_rows(load, alpha, gamma, scale, B, [&](int i, const QRow& r) {
+      dq1[i] = r.g1;
+      dq2[i] = r.g2;
+      if (fuse) { dqs[0][i] = r.g1; dqs[1][i] = r.g2; }
+    });
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
+  float mean[1] = {acc};
+  loss_block_mean<1>(mean, red, B);
   if (threadIdx.x == 0) {
-    loss_acc[0] += (red[0] + red[1] + red[2] + red[3]) / B;
+    loss_acc[0] += mean[0];
     // commit the update's counter bump (replay/noise counter + both Adam
     // step counters): this single block runs after both counter readers
     // (gather2 / tg_fwd2 key on ctr+1) and before both Adam applications
@@ -1877,37 +2174,25 @@ void piloss2_kernel(const float* __restrict__ q1, const float* __restrict__ q2,
                     const float* __restrict__ wt3_1,
                     float* __restrict__ dy2_0, float* __restrict__ dy2_1,
                     int h2) {
-  __shared__ float red[4], redl[4];
+  __shared__ float red[2][4];   // loss | logp
   __shared__ float dqs[2][LOSS_MAXB];
   const float alpha = alpha_dev ? alpha_dev[0] : alpha_host;
   const bool fuse = dy2_0 != nullptr;
-  float acc = 0.f, laux = 0.f;
-  for (int i = threadIdx.x; i < B; i += blockDim.x) {
-    float a = q1[i], b = q2[i];
-    acc += alpha * logp[i] - fminf(a, b);
-    laux += logp[i];
-    float g1, g2;
-    if (a < b)      { g1 = -1.f; g2 = 0.f; }
-    else if (b < a) { g1 = 0.f;  g2 = -1.f; }
-    else            { g1 = -0.5f; g2 = -0.5f; }
-    dq1[i] = g1 / B;
-    dq2[i] = g2 / B;
-    if (fuse) { dqs[0][i] = g1 / B; dqs[1][i] = g2 / B; }
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    acc += __shfl_down(acc, off);
-    laux += __shfl_down(laux, off);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    red[threadIdx.x >> 6] = acc;
-    redl[threadIdx.x >> 6] = laux;
-  }
-  __syncthreads();
+  float acc[2];
+  auto load = [&](int i) {
+    QVals v = {};
+    v.q1 = q1[i]; v.q2 = q2[i]; v.lpn = logp[i];
+    return v;
+  };
+  piloss_rows(acc, load, alpha, B, [&](int i, const PiRow& r) {
+    dq1[i] = r.g1;
+    dq2[i] = r.g2;
+    if (fuse) { dqs[0][i] = r.g1; dqs[1][i] = r.g2; }
+  });
+  loss_block_mean<2>(acc, red, B);
   if (threadIdx.x == 0) {
-    loss_acc[0] += (red[0] + red[1] + red[2] + red[3]) / B;
-    if (mean_logp)
-      mean_logp[0] = (redl[0] + redl[1] + redl[2] + redl[3]) / B;
+    loss_acc[0] += acc[0];
+    if (mean_logp) mean_logp[0] = acc[1];
   }
   if (fuse) {
     const int64_t total = (int64_t)B * h2;
@@ -3091,6 +3376,164 @@ void piloss2(torch::Tensor q1, torch::Tensor q2, torch::Tensor logp,
                      fuse ? dy2_1->data_ptr<float>() : nullptr, (int)h2);
 }
 
+// ---------------------------------------------------------------------------
+// mgemm_r1 with the column computed from a loss kernel's inputs: the launch
+// replaces qloss2 + the K=1 dgrad + the masked dgrad (mgemm_r1_qloss), or
+// piloss2 + mgemm_r1 (mgemm_r1_piloss), bit for bit.  Only the small-shape
+// bf16 kernel has the folded form; mgemm_r1_fold_ok is its host gate.
+// ---------------------------------------------------------------------------
+
+bool mgemm_r1_fold_ok(int64_t M, int64_t K) {
+  return M >= 1 && K >= 1 && small_gate(*g_bf16_flag, 1, 1, M, K, false, 0);
+}
+
+// the operands the two folded entries share with mgemm_r1 (nz == 2)
+static void fold_gemm_args(MGemm& g, const char* op,
+                           const std::vector<torch::Tensor>& rows,
+                           const std::vector<torch::Tensor>& ws,
+                           const std::vector<torch::Tensor>& ys,
+                           const std::vector<torch::Tensor>& masks,
+                           int64_t M, int64_t N, int64_t K, int64_t ldy) {
+  TORCH_CHECK(rows.size() == 2 && ws.size() == 2 && ys.size() == 2
+              && masks.size() == 2, op, ": exactly 2 problems (nz == 2)");
+  TORCH_CHECK(M >= 1 && N >= 1 && K >= 1 && ldy >= N, op, ": shape");
+  TORCH_CHECK(mgemm_r1_fold_ok(M, K), op, ": outside the small-shape gate "
+              "(bf16 compute, M <= 128, K <= ", SKMAX, ", small mode on)");
+  g.M = (int)M; g.N = (int)N; g.K = (int)K;
+  g.lda = (int)K; g.ldy = (int)ldy;
+  g.nz = 2; g.k_chunk = (int)K; g.part = nullptr;
+  for (int z = 0; z < 2; ++z) {
+    need_f32(rows[z], 0, op, "row");
+    TORCH_CHECK(rows[z].numel() == K
+                && ((uintptr_t)rows[z].data_ptr<float>() & 15) == 0,
+                op, ": row ", z, " must be K floats, 16-byte aligned");
+    need_f32(ws[z], 0, op, "w");
+    TORCH_CHECK(ws[z].numel() == N * K, op, ": w ", z);
+    need_f32(masks[z], 0, op, "mask");
+    TORCH_CHECK(masks[z].numel() == M * K, op, ": mask ", z);
+    TORCH_CHECK(ys[z].is_cuda() && ys[z].scalar_type() == torch::kFloat32
+                && ys[z].numel() >= (M - 1) * ldy + N, op, ": y ", z);
+    g.p[z].r1_row = rows[z].data_ptr<float>();
+    g.p[z].w = ws[z].data_ptr<float>();
+    g.p[z].y = ys[z].data_ptr<float>();
+    g.p[z].mask = masks[z].data_ptr<float>();
+  }
+}
+
+static void need_vecM(const torch::Tensor& t, int64_t M, const char* op,
+                      const char* name) {
+  need_f32(t, M, op, name);
+  TORCH_CHECK(t.numel() == M, op, ": ", name, " must hold M = ", M,
+              " elements");
+}
+
+template <int LF>
+static void launch_small_fold(const MGemm& g, const LossFold& lf) {
+  constexpr int T = 32;
+  // the reducing block holds one batch row per thread (fold_preload)
+  TORCH_CHECK(g.M <= 256, "folded loss: M must not exceed the block size");
+  dim3 grid((unsigned)((g.M + T - 1) / T), (unsigned)((g.N + T - 1) / T), 2);
+  hipLaunchKernelGGL((mgemm_small_kernel<T, T, true, false, false, true, LF,
+                                         LossFold>),
+                     grid, dim3(256), 0, stream(), g, lf);
+}
+
+void mgemm_r1_qloss(torch::Tensor q1, torch::Tensor q2, torch::Tensor q1t,
+                    torch::Tensor q2t, torch::Tensor logp_next,
+                    torch::Tensor rew, torch::Tensor done,
+                    c10::optional<torch::Tensor> alpha_dev, double alpha_host,
+                    torch::Tensor loss_acc, torch::Tensor dq1,
+                    torch::Tensor dq2, double gamma, double scale,
+                    c10::optional<torch::Tensor> bump0,
+                    c10::optional<torch::Tensor> bump1,
+                    c10::optional<torch::Tensor> bump2,
+                    std::vector<torch::Tensor> rows,
+                    std::vector<torch::Tensor> ws,
+                    std::vector<torch::Tensor> ys,
+                    std::vector<torch::Tensor> masks,
+                    std::vector<torch::Tensor> outers,
+                    int64_t M, int64_t N, int64_t K, int64_t ldy) {
+  const char* op = "mgemm_r1_qloss";
+  MGemm g{};
+  fold_gemm_args(g, op, rows, ws, ys, masks, M, N, K, ldy);
+  need_vecM(q1, M, op, "q1");
+  need_vecM(q2, M, op, "q2");
+  need_vecM(q1t, M, op, "q1t");
+  need_vecM(q2t, M, op, "q2t");
+  need_vecM(logp_next, M, op, "logp_next");
+  need_vecM(rew, M, op, "rew");
+  need_vecM(done, M, op, "done");
+  need_vecM(dq1, M, op, "dq1");
+  need_vecM(dq2, M, op, "dq2");
+  need_scalar_f32(loss_acc, op, "loss_acc");
+  if (alpha_dev.has_value()) need_scalar_f32(*alpha_dev, op, "alpha_dev");
+  if (bump0.has_value()) need_scalar_i64(*bump0, op, "bump0");
+  if (bump1.has_value()) need_scalar_i64(*bump1, op, "bump1");
+  if (bump2.has_value()) need_scalar_i64(*bump2, op, "bump2");
+  TORCH_CHECK(outers.size() == 2, op, ": exactly 2 outer-product buffers");
+  for (int z = 0; z < 2; ++z) {
+    need_f32(outers[z], M * K, op, "outer");
+    TORCH_CHECK(((uintptr_t)outers[z].data_ptr<float>() & 15) == 0, op,
+                ": outer ", z, " must be 16-byte aligned");
+  }
+  auto iptr = [](const c10::optional<torch::Tensor>& t) -> int64_t* {
+    return t.has_value() ? t->data_ptr<int64_t>() : nullptr;
+  };
+  LossFold lf{};
+  lf.in = QIn{q1.data_ptr<float>(), q2.data_ptr<float>(),
+              q1t.data_ptr<float>(), q2t.data_ptr<float>(),
+              logp_next.data_ptr<float>(), rew.data_ptr<float>(),
+              done.data_ptr<float>()};
+  lf.alpha_dev = fptr(alpha_dev);
+  lf.alpha_host = (float)alpha_host;
+  lf.gamma = (float)gamma;
+  lf.scale = (float)scale;
+  lf.loss_acc = loss_acc.data_ptr<float>();
+  lf.dq[0] = dq1.data_ptr<float>();
+  lf.dq[1] = dq2.data_ptr<float>();
+  lf.outer[0] = outers[0].data_ptr<float>();
+  lf.outer[1] = outers[1].data_ptr<float>();
+  lf.bump[0] = iptr(bump0);
+  lf.bump[1] = iptr(bump1);
+  lf.bump[2] = iptr(bump2);
+  launch_small_fold<2>(g, lf);
+}
+
+void mgemm_r1_piloss(torch::Tensor q1, torch::Tensor q2, torch::Tensor logp,
+                     c10::optional<torch::Tensor> alpha_dev,
+                     double alpha_host, torch::Tensor loss_acc,
+                     c10::optional<torch::Tensor> mean_logp,
+                     torch::Tensor dq1, torch::Tensor dq2,
+                     std::vector<torch::Tensor> rows,
+                     std::vector<torch::Tensor> ws,
+                     std::vector<torch::Tensor> ys,
+                     std::vector<torch::Tensor> masks,
+                     int64_t M, int64_t N, int64_t K, int64_t ldy) {
+  const char* op = "mgemm_r1_piloss";
+  MGemm g{};
+  fold_gemm_args(g, op, rows, ws, ys, masks, M, N, K, ldy);
+  need_vecM(q1, M, op, "q1");
+  need_vecM(q2, M, op, "q2");
+  need_vecM(logp, M, op, "logp");
+  need_vecM(dq1, M, op, "dq1");
+  need_vecM(dq2, M, op, "dq2");
+  need_scalar_f32(loss_acc, op, "loss_acc");
+  if (alpha_dev.has_value()) need_scalar_f32(*alpha_dev, op, "alpha_dev");
+  if (mean_logp.has_value()) need_scalar_f32(*mean_logp, op, "mean_logp");
+  LossFold lf{};
+  lf.in.q1 = q1.data_ptr<float>();
+  lf.in.q2 = q2.data_ptr<float>();
+  lf.in.lpn = logp.data_ptr<float>();
+  lf.alpha_dev = fptr(alpha_dev);
+  lf.alpha_host = (float)alpha_host;
+  lf.loss_acc = loss_acc.data_ptr<float>();
+  lf.mean_logp = mean_logp.has_value() ? mean_logp->data_ptr<float>()
+                                         : nullptr;
+  lf.dq[0] = dq1.data_ptr<float>();
+  lf.dq[1] = dq2.data_ptr<float>();
+  launch_small_fold<1>(g, lf);
+}
+
 void adam_t(torch::Tensor p, torch::Tensor g, torch::Tensor m,
             torch::Tensor v, torch::Tensor step, double lr, double b1,
             double b2, double eps, double wd,
@@ -3388,6 +3831,12 @@ void register_fused(pybind11::module_& m) {
         "multi-problem MFMA GEMM (fwd-form, strided, masked, sum2)");
   m.def("mgemm_r1", &fused::mgemm_r1,
         "masked GEMM whose A operand is a rank-1 product formed on read");
+  m.def("mgemm_r1_qloss", &fused::mgemm_r1_qloss,
+        "qloss2 + K=1 dgrad + masked dgrad in one small-shape launch");
+  m.def("mgemm_r1_piloss", &fused::mgemm_r1_piloss,
+        "piloss2 + mgemm_r1 in one small-shape launch");
+  m.def("mgemm_r1_fold_ok", &fused::mgemm_r1_fold_ok,
+        "host-only: do (M, K) pass the gate of the two folded entries");
   m.def("mgemm_small_mode", &fused::mgemm_small_mode,
         "set TAC_AMD_MGEMM_SMALL's mode (0 = pipelined kernel only), "
         "returns the previous mode");
