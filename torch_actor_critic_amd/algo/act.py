@@ -52,6 +52,11 @@ class ActKernel:
         self.ev = torch.cuda.Event()
         import os
         self._pinned_ok = os.environ.get("TAC_AMD_ACT_PINNED", "1") != "0"
+        # TAC_AMD_ACT_SYNC: 1 (default) drives the pinned path with one
+        # native call per env step (copy in, launch, spin, copy out in
+        # C++), 0 keeps the launch and the spin in Python
+        self._sync = os.environ.get("TAC_AMD_ACT_SYNC", "1") != "0"
+        self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
         # pre-marshalled launch handle (referenced tensors stay alive via
         # self.*): one int-arg pybind call per env step
         self._handle = self.ext.act_prepare(
@@ -60,21 +65,31 @@ class ActKernel:
             self.seed, self.act_limit, self.lo, self.hi)
 
     def act(self, state: np.ndarray) -> np.ndarray:
-        self.obs_pin.copy_(torch.from_numpy(np.asarray(state,
-                                                       dtype=np.float32)))
+        # zero-copy I/O on the pinned path: the kernel READS the
+        # observation from and WRITES the action + a system-scope
+        # completion flag to host-pinned memory; the host spins on the
+        # flag — no H2D/D2H copies, no event sync
+        if self._pinned_ok and self._sync:
+            obs = np.ascontiguousarray(state, dtype=np.float32).reshape(-1)
+            out = np.empty(self.act_dim, dtype=np.float32)
+            if self.ext.act_sync(self._handle, obs, out):
+                return out
+            # flag never landed: drain the stream once, then give up on
+            # the pinned path for this session (obs_pin holds the state)
+            torch.cuda.synchronize()
+            if self.flag_np[0] != 0:
+                return self.act_pin.numpy().copy()
+            self._pinned_ok = False
+        else:
+            self.obs_pin.copy_(torch.from_numpy(
+                np.asarray(state, dtype=np.float32)))
         if self._pinned_ok:
-            # zero-copy I/O: the kernel READS the observation from and
-            # WRITES the action + a system-scope completion flag to
-            # host-pinned memory; the host spins on the flag — no H2D/D2H
-            # copies, no event sync
             self.flag_pin[0] = 0
             self.ext.act_fire(self._handle)
             fl = self.flag_np
             for _ in range(2_000_000):
                 if fl[0] != 0:
                     return self.act_pin.numpy().copy()
-            # flag never landed: drain the stream once, then give up on
-            # the pinned path for this session
             torch.cuda.synchronize()
             if fl[0] != 0:
                 return self.act_pin.numpy().copy()

@@ -24,11 +24,14 @@
 
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
+#include <pybind11/numpy.h>
 
 #include <algorithm>
+#include <cstdint>
 #include <utility>
 #include <vector>
 
+#include "act_sync.h"
 #include "replay_draw.h"
 
 namespace fused {
@@ -2294,6 +2297,287 @@ void act_kernel(ActArgs a, ActPinned hp) {
 }
 
 // ---------------------------------------------------------------------------
+// Latency-shaped form of act_kernel: the same arithmetic per output neuron,
+// in the same order, but the weights reach it differently.  act_kernel has
+// each thread walk its own fp32 row straight from global memory, so a wave
+// load touches 64 lines for 16 bytes each and every loop iteration ends on
+// a full wait (measured: 7.5 us in layer 1 and 4.5 us in the heads of an
+// 18.6 us launch).  Here every load the kernel will ever need is addressed
+// without the observation, so it is issued at kernel start, coalesced
+// (consecutive lanes read consecutive addresses), and parked in registers:
+//   * the observation and the counter (first, so their waits stay short);
+//   * all biases;
+//   * layer 0's [H, O] matrix as flat dwords (O is odd in practice);
+//   * the hidden layers as a stream of K slabs, [H rows] x [64 columns],
+//     two slabs in flight in two register sets, refilled as they drain;
+//   * both heads' rows as flat dwords.
+// Each piece goes through LDS once (slab rows padded to 68 floats, so the
+// 16-byte row reads of 16 lanes fall on 64 different banks) and thread t
+// then reads row t from LDS exactly as act_kernel reads it from memory.
+// The mu rows run on wave 0 and the log-std rows on wave 1.
+//
+// The block is one wave per SIMD, so every instruction is paid in full:
+// addresses are a per-thread offset plus uniform or immediate parts, and
+// tails are handled by clamping an index (a repeated load or store of the
+// same value), not by branching per element.
+//
+// Roundings follow what the shipped act_kernel compiles to: in the groups
+// of four every product is rounded, ((p0 + p1) + p2) + p3, then acc +=
+// group; the scalar K tail, both head rows and mu + exp(ls) * eps are
+// fused multiply-adds.
+//
+// Gate (act_fast_fits): 1..4 layers; widths 4..256, multiples of 4; hidden
+// layers (L >= 1) with K a multiple of 64 and H a multiple of 16; the last
+// width a power of two; H0 * O <= 9216; A <= 64 and A * K_last <= 2048;
+// hidden weights 16-byte aligned.
+// ---------------------------------------------------------------------------
+
+constexpr int ACTF_L0 = 36;               // layer-0 dwords per thread
+constexpr int ACTF_KS = 64;               // hidden-layer slab columns
+constexpr int ACTF_SV = ACTF_KS / 4;      // float4 per thread per slab
+constexpr int ACTF_SS = ACTF_KS + 4;      // slab row stride in LDS
+constexpr int ACTF_HV = 8;                // dwords per thread per head
+constexpr int ACTF_HL = 2 * ACTF_HV * 256 + 128 * 4;
+
+struct ActfLds {
+  float act[2][256];
+  float bias[ACT_MAXL][256];
+  float w0[ACTF_L0 * 256];
+  float slab[256 * ACTF_SS];
+  float hd[ACTF_HL];
+  float ls[64];
+  unsigned long long ctr;
+};
+
+// position in the hidden-layer slab stream, with that layer's shape
+struct ActfCur {
+  int L, k0, K, H;
+  const float* w;
+};
+
+DEVINL void actf_shape(const ActArgs& a, ActfCur& c) {
+  // selects over statically indexed kernel arguments: no memory round trip
+  c.K = c.L == 1 ? a.width[0] : c.L == 2 ? a.width[1] : a.width[2];
+  c.H = c.L == 1 ? a.width[1] : c.L == 2 ? a.width[2] : a.width[3];
+  c.w = c.L == 1 ? a.w[1] : c.L == 2 ? a.w[2] : a.w[3];
+}
+
+DEVINL ActfCur actf_next(const ActArgs& a, ActfCur c) {
+  if (c.L < a.n_layers) {
+    c.k0 += ACTF_KS;
+    if (c.k0 >= c.K) { ++c.L; c.k0 = 0; actf_shape(a, c); }
+  }
+  return c;
+}
+
+// Slab element j of thread tid is row (tid >> 4) + 16 j, float4 column
+// tid & 15.  FULL: H == 256, nothing to guard; otherwise rows in whole
+// sixteens (H % 16 == 0), a uniform guard per j.
+template <bool FULL>
+DEVINL void actf_issue(f32x4 (&R)[ACTF_SV], const ActfCur& cu, int tid) {
+  const unsigned vo = (unsigned)(tid >> 4) * cu.K + (tid & 15) * 4;
+#pragma unroll
+  for (int j = 0; j < ACTF_SV; ++j) {
+    if (FULL || 16 * j < cu.H) {
+      const float* p = cu.w + cu.k0 + (int64_t)(16 * j) * cu.K;   // uniform
+      R[j] = *reinterpret_cast<const f32x4*>(p + vo);
+    }
+  }
+}
+
+template <bool FULL>
+DEVINL void actf_commit(const f32x4 (&R)[ACTF_SV], float* slab,
+                        const ActfCur& cu, int tid) {
+  float* d = slab + (tid >> 4) * ACTF_SS + (tid & 15) * 4;
+#pragma unroll
+  for (int j = 0; j < ACTF_SV; ++j)
+    if (FULL || 16 * j < cu.H)
+      *reinterpret_cast<f32x4*>(d + 16 * j * ACTF_SS) = R[j];
+}
+
+__global__ __launch_bounds__(256)
+void act_fast_kernel(ActArgs a, ActPinned hp) {
+#pragma clang fp contract(off)
+  __shared__ __attribute__((aligned(16))) ActfLds s;
+  const int tid = threadIdx.x;
+  const int O = a.O, A = a.A, nl = a.n_layers;
+  const int H0 = a.width[0];
+  const int KL = nl == 1 ? a.width[0] : nl == 2 ? a.width[1]
+               : nl == 3 ? a.width[2] : a.width[3];
+
+  // ---- every load, before anything waits --------------------------------
+  const float xo = a.x[tid < O ? tid : 0];
+  const long long c_old = a.ctr[0];
+  float br[ACT_MAXL];
+#pragma unroll
+  for (int L = 0; L < ACT_MAXL; ++L)
+    br[L] = L < nl ? a.b[L][tid < a.width[L] ? tid : 0] : 0.f;
+  // head bias: mu rows on wave 0, log-std rows on wave 1
+  const int hl = tid & 63;
+  const bool h_on = tid < 128 && hl < A;
+  float hv = (tid < 64 ? a.bmu : a.bls)[hl < A ? hl : 0];
+
+  // layer 0, flat; rounds in groups of six, indices clamped to the last
+  float v0[ACTF_L0];
+  const int n0 = H0 * O;
+  const int r0 = (n0 + 255) >> 8;
+#pragma unroll
+  for (int g = 0; g < ACTF_L0 / 6; ++g) {
+    if (6 * g < r0) {
+#pragma unroll
+      for (int j = 6 * g; j < 6 * g + 6; ++j)
+        v0[j] = a.w[0][min(tid + 256 * j, n0 - 1)];
+    }
+  }
+
+  f32x4 RA[ACTF_SV], RB[ACTF_SV];
+  ActfCur cu{1, 0, 0, 0, nullptr};
+  actf_shape(a, cu);
+  auto issue = [&](f32x4 (&R)[ACTF_SV], const ActfCur& c) {
+    if (c.L < nl) {
+      if (c.H == 256) actf_issue<true>(R, c, tid);
+      else actf_issue<false>(R, c, tid);
+    }
+  };
+  issue(RA, cu);
+  issue(RB, actf_next(a, cu));
+
+  // heads, flat per head; rounds in groups of four, indices clamped
+  float hm[ACTF_HV], hs[ACTF_HV];
+  const int nh = A * KL;
+  const int rh = (nh + 255) >> 8;
+#pragma unroll
+  for (int g = 0; g < ACTF_HV / 4; ++g) {
+    if (4 * g < rh) {
+#pragma unroll
+      for (int j = 4 * g; j < 4 * g + 4; ++j) {
+        const int idx = min(tid + 256 * j, nh - 1);
+        hm[j] = a.wmu[idx];
+        hs[j] = a.wls[idx];
+      }
+    }
+  }
+
+  // ---- observation, biases, layer 0 -> LDS ------------------------------
+  if (tid < O) s.act[0][tid] = xo;
+#pragma unroll
+  for (int L = 0; L < ACT_MAXL; ++L) s.bias[L][tid] = br[L];
+  if (tid == 0) {
+    const long long c_new = c_old + 1;
+    a.ctr[0] = c_new;
+    s.ctr = (unsigned long long)c_new;
+  }
+#pragma unroll
+  for (int g = 0; g < ACTF_L0 / 6; ++g) {
+    if (6 * g < r0) {
+#pragma unroll
+      for (int j = 6 * g; j < 6 * g + 6; ++j)
+        s.w0[min(tid + 256 * j, n0 - 1)] = v0[j];
+    }
+  }
+  __syncthreads();
+
+  int cur = 1;
+  {
+    float acc = br[0];
+    if (tid < H0) {
+      const float* wr = s.w0 + tid * O;
+      const float* x = s.act[0];
+      int k = 0;
+      for (; k + 4 <= O; k += 4)
+        acc += wr[k] * x[k] + wr[k+1] * x[k+1]
+             + wr[k+2] * x[k+2] + wr[k+3] * x[k+3];
+      for (; k < O; ++k) acc = __builtin_fmaf(wr[k], x[k], acc);
+      s.act[1][tid] = fmaxf(acc, 0.f);
+    }
+  }
+
+  // ---- hidden layers: the slab stream ------------------------------------
+  float acc = br[1];
+  auto slab_step = [&](f32x4 (&R)[ACTF_SV]) {
+    if (cu.H == 256) actf_commit<true>(R, s.slab, cu, tid);
+    else actf_commit<false>(R, s.slab, cu, tid);
+    __syncthreads();   // slab (and the previous layer's output) visible
+    issue(R, actf_next(a, actf_next(a, cu)));
+    if (tid < cu.H) {
+      const f32x4* wr = reinterpret_cast<const f32x4*>(s.slab + tid * ACTF_SS);
+      const f32x4* x = reinterpret_cast<const f32x4*>(s.act[cur] + cu.k0);
+#pragma unroll
+      for (int g = 0; g < ACTF_SV; ++g) {
+        const f32x4 w = wr[g], h = x[g];
+        acc += w.x * h.x + w.y * h.y + w.z * h.z + w.w * h.w;
+      }
+    }
+    if (cu.k0 + ACTF_KS >= cu.K) {   // layer done
+      if (tid < cu.H) s.act[1 - cur][tid] = fmaxf(acc, 0.f);
+      cur ^= 1;
+      acc = s.bias[cu.L + 1 < ACT_MAXL ? cu.L + 1 : 0][tid];
+    }
+    __syncthreads();   // slab free for the next commit
+    cu = actf_next(a, cu);
+  };
+  while (cu.L < nl) {
+    slab_step(RA);
+    if (cu.L >= nl) break;
+    slab_step(RB);
+  }
+
+  // ---- heads -------------------------------------------------------------
+  const int HS = KL + 4;
+  {
+    const int sh = 31 - __builtin_clz(KL);   // KL is a power of two
+    float* hd_ls = s.hd + A * HS;
+#pragma unroll
+    for (int g = 0; g < ACTF_HV / 4; ++g) {
+      if (4 * g < rh) {
+#pragma unroll
+        for (int j = 4 * g; j < 4 * g + 4; ++j) {
+          const int idx = min(tid + 256 * j, nh - 1);
+          const int d = (idx >> sh) * HS + (idx & (KL - 1));
+          s.hd[d] = hm[j];
+          hd_ls[d] = hs[j];
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (h_on) {
+    const int row = tid < 64 ? hl : A + hl;
+    const f32x4* wr = reinterpret_cast<const f32x4*>(s.hd + row * HS);
+    const f32x4* x = reinterpret_cast<const f32x4*>(s.act[cur]);
+    for (int g = 0; g < (KL >> 2); ++g) {
+      const f32x4 w = wr[g], h = x[g];
+      hv = __builtin_fmaf(w.x, h.x, hv);
+      hv = __builtin_fmaf(w.y, h.y, hv);
+      hv = __builtin_fmaf(w.z, h.z, hv);
+      hv = __builtin_fmaf(w.w, h.w, hv);
+    }
+    if (tid >= 64) s.ls[hl] = hv;
+  }
+  __syncthreads();
+  if (tid < A) {
+    const float mu = hv;
+    float ls = s.ls[tid];
+    ls = fminf(fmaxf(ls, a.lo), a.hi);
+    Philox4 r = philox4(a.seed ^ 0x517cc1b727220a95ull, s.ctr, (uint64_t)tid);
+    float eps = philox_normal(r.x, r.y);
+    // act_kernel's mu + exp(ls) * eps compiles to one fused multiply-add
+    float act = tanhf(__builtin_fmaf(expf(ls), eps, mu)) * a.act_limit;
+    a.action[tid] = act;
+    if (hp.out_host) hp.out_host[tid] = act;
+  }
+  if (hp.flag_host) {
+    __threadfence_system();
+    __syncthreads();
+    if (tid == 0) {
+      __threadfence_system();
+      *(volatile int*)hp.flag_host = 1;
+    }
+  }
+}
+
+
+// ---------------------------------------------------------------------------
 // Batched whole-policy action kernel (evaluation path): the actor forward
 // for N states in ONE launch.  Each block owns a tile of ACTB_R rows staged
 // in LDS; each thread owns one output neuron, reads its weight row once and
@@ -3599,11 +3883,15 @@ torch::Tensor tg_eps(int64_t ctr_val, int64_t seed, int64_t R, int64_t A,
   return out;
 }
 
-void act_step(torch::Tensor x, std::vector<torch::Tensor> ws,
-              std::vector<torch::Tensor> bs, torch::Tensor wmu,
-              torch::Tensor bmu, torch::Tensor wls, torch::Tensor bls,
-              torch::Tensor action, torch::Tensor ctr, int64_t seed,
-              double act_limit, double lo, double hi) {
+// The one marshalling of a single-state act launch's arguments.
+static ActArgs act_args(const torch::Tensor& x,
+                        const std::vector<torch::Tensor>& ws,
+                        const std::vector<torch::Tensor>& bs,
+                        const torch::Tensor& wmu, const torch::Tensor& bmu,
+                        const torch::Tensor& wls, const torch::Tensor& bls,
+                        const torch::Tensor& action,
+                        const torch::Tensor& ctr, int64_t seed,
+                        double act_limit, double lo, double hi) {
   ActArgs a{};
   a.n_layers = (int)ws.size();
   TORCH_CHECK(a.n_layers <= ACT_MAXL);
@@ -3629,8 +3917,90 @@ void act_step(torch::Tensor x, std::vector<torch::Tensor> ws,
   a.act_limit = (float)act_limit;
   a.lo = (float)lo;
   a.hi = (float)hi;
-  hipLaunchKernelGGL(act_kernel, dim3(1), dim3(256), 0, stream(), a,
-                     ActPinned{nullptr, nullptr});
+  return a;
+}
+
+// TAC_AMD_ACT_FAST: 1 (default) sends single-state act launches inside
+// act_fast_kernel's gate to it, 0 keeps act_kernel for everything.  A
+// plain global so act_fast_mode() can flip it inside one process.
+static int g_act_fast = -1;
+
+static bool act_fast_mode_get() {
+  if (g_act_fast < 0) {
+    const char* e = getenv("TAC_AMD_ACT_FAST");
+    g_act_fast = e ? (atoi(e) != 0) : 1;
+  }
+  return g_act_fast != 0;
+}
+
+int64_t act_fast_mode(int64_t mode) {
+  const int prev = act_fast_mode_get();
+  TORCH_CHECK(mode == 0 || mode == 1, "act_fast_mode: 0 or 1");
+  g_act_fast = (int)mode;
+  return prev;
+}
+
+// Host-only gate of act_fast_kernel on shapes: obs width, trunk widths,
+// action width (the limits are the kernel's register and LDS budgets).
+static bool act_fast_shape_ok(int O, const int* width, int n_layers, int A) {
+  if (n_layers < 1 || n_layers > ACT_MAXL) return false;
+  if (O < 1 || O > 256 || A < 1 || A > 64) return false;
+  for (int L = 0; L < n_layers; ++L)
+    if (width[L] < 4 || width[L] > 256 || width[L] % 4 != 0) return false;
+  for (int L = 1; L < n_layers; ++L)   // whole 64-column slabs, rows in 16s
+    if (width[L - 1] % ACTF_KS != 0 || width[L] % 16 != 0) return false;
+  const int KL = width[n_layers - 1];
+  if ((KL & (KL - 1)) != 0) return false;
+  if ((int64_t)width[0] * O > ACTF_L0 * 256) return false;
+  if ((int64_t)A * KL > ACTF_HV * 256) return false;
+  return true;
+}
+
+bool act_fast_ok(int64_t obs_dim, std::vector<int64_t> widths,
+                 int64_t act_dim) {
+  if (widths.empty() || widths.size() > (size_t)ACT_MAXL) return false;
+  if (obs_dim < 1 || obs_dim > 256 || act_dim < 1 || act_dim > 64)
+    return false;
+  int w[ACT_MAXL] = {};
+  for (size_t L = 0; L < widths.size(); ++L) {
+    if (widths[L] < 1 || widths[L] > 256) return false;
+    w[L] = (int)widths[L];
+  }
+  return act_fast_shape_ok((int)obs_dim, w, (int)widths.size(),
+                           (int)act_dim);
+}
+
+// shape gate plus what only the pointers tell: the hidden layers are read
+// as 16-byte vectors
+static bool act_fast_fits(const ActArgs& a) {
+  if (!act_fast_shape_ok(a.O, a.width, a.n_layers, a.A)) return false;
+  for (int L = 1; L < a.n_layers; ++L)
+    if (reinterpret_cast<uintptr_t>(a.w[L]) % 16 != 0) return false;
+  return true;
+}
+
+static bool g_act_last_fast = false;
+
+// every single-state act launch goes through here
+static void act_launch(const ActArgs& a, const ActPinned& hp, bool fits) {
+  g_act_last_fast = fits && act_fast_mode_get();
+  if (g_act_last_fast)
+    hipLaunchKernelGGL(act_fast_kernel, dim3(1), dim3(256), 0, stream(), a,
+                       hp);
+  else
+    hipLaunchKernelGGL(act_kernel, dim3(1), dim3(256), 0, stream(), a, hp);
+}
+
+bool act_last_fast() { return g_act_last_fast; }
+
+void act_step(torch::Tensor x, std::vector<torch::Tensor> ws,
+              std::vector<torch::Tensor> bs, torch::Tensor wmu,
+              torch::Tensor bmu, torch::Tensor wls, torch::Tensor bls,
+              torch::Tensor action, torch::Tensor ctr, int64_t seed,
+              double act_limit, double lo, double hi) {
+  const ActArgs a = act_args(x, ws, bs, wmu, bmu, wls, bls, action, ctr,
+                             seed, act_limit, lo, hi);
+  act_launch(a, ActPinned{nullptr, nullptr}, act_fast_fits(a));
 }
 
 // act_step writing the action AND a completion flag to host-pinned
@@ -3644,34 +4014,10 @@ void act_step_pinned(torch::Tensor x, std::vector<torch::Tensor> ws,
                      double lo, double hi) {
   TORCH_CHECK(out_host.is_pinned() && flag_host.is_pinned(),
               "host buffers must be pinned");
-  ActArgs a{};
-  a.n_layers = (int)ws.size();
-  TORCH_CHECK(a.n_layers <= ACT_MAXL);
-  a.x = x.data_ptr<float>();
-  a.O = (int)x.numel();
-  a.A = (int)action.numel();
-  int maxw = a.O;
-  for (int L = 0; L < a.n_layers; ++L) {
-    a.w[L] = ws[L].data_ptr<float>();
-    a.b[L] = bs[L].data_ptr<float>();
-    a.width[L] = (int)ws[L].size(0);
-    TORCH_CHECK(a.width[L] <= 256);
-    maxw = std::max(maxw, a.width[L]);
-  }
-  TORCH_CHECK(maxw <= ACT_MAXW && a.A <= 256);
-  a.wmu = wmu.data_ptr<float>();
-  a.bmu = bmu.data_ptr<float>();
-  a.wls = wls.data_ptr<float>();
-  a.bls = bls.data_ptr<float>();
-  a.action = action.data_ptr<float>();
-  a.ctr = ctr.data_ptr<int64_t>();
-  a.seed = (uint64_t)seed;
-  a.act_limit = (float)act_limit;
-  a.lo = (float)lo;
-  a.hi = (float)hi;
-  hipLaunchKernelGGL(act_kernel, dim3(1), dim3(256), 0, stream(), a,
-                     ActPinned{out_host.data_ptr<float>(),
-                               flag_host.data_ptr<int>()});
+  const ActArgs a = act_args(x, ws, bs, wmu, bmu, wls, bls, action, ctr,
+                             seed, act_limit, lo, hi);
+  act_launch(a, ActPinned{out_host.data_ptr<float>(),
+                          flag_host.data_ptr<int>()}, act_fast_fits(a));
 }
 
 void bump3(torch::Tensor a, c10::optional<torch::Tensor> b,
@@ -3685,7 +4031,13 @@ void bump3(torch::Tensor a, c10::optional<torch::Tensor> b,
 // Pre-marshalled acting: the ActArgs are built once (act_prepare) and
 // fired with a single-int pybind call per env step (act_fire) — the
 // 13-argument marshalling otherwise costs microseconds per step.
-static std::vector<std::pair<ActArgs, ActPinned>> g_act_handles;
+struct ActHandle {
+  ActArgs a;
+  ActPinned hp;
+  bool fits;       // act_fast_fits(a), decided once: the pointers are fixed
+  bool x_pinned;   // act_sync writes the observation through a.x
+};
+static std::vector<ActHandle> g_act_handles;
 
 int64_t act_prepare(torch::Tensor x, std::vector<torch::Tensor> ws,
                     std::vector<torch::Tensor> bs, torch::Tensor wmu,
@@ -3694,40 +4046,46 @@ int64_t act_prepare(torch::Tensor x, std::vector<torch::Tensor> ws,
                     torch::Tensor flag_host, torch::Tensor ctr,
                     int64_t seed, double act_limit, double lo, double hi) {
   TORCH_CHECK(out_host.is_pinned() && flag_host.is_pinned());
-  ActArgs a{};
-  a.n_layers = (int)ws.size();
-  TORCH_CHECK(a.n_layers <= ACT_MAXL);
-  a.x = x.data_ptr<float>();
-  a.O = (int)x.numel();
-  a.A = (int)action.numel();
-  int maxw = a.O;
-  for (int L = 0; L < a.n_layers; ++L) {
-    a.w[L] = ws[L].data_ptr<float>();
-    a.b[L] = bs[L].data_ptr<float>();
-    a.width[L] = (int)ws[L].size(0);
-    TORCH_CHECK(a.width[L] <= 256);
-    maxw = std::max(maxw, a.width[L]);
-  }
-  TORCH_CHECK(maxw <= ACT_MAXW && a.A <= 256);
-  a.wmu = wmu.data_ptr<float>();
-  a.bmu = bmu.data_ptr<float>();
-  a.wls = wls.data_ptr<float>();
-  a.bls = bls.data_ptr<float>();
-  a.action = action.data_ptr<float>();
-  a.ctr = ctr.data_ptr<int64_t>();
-  a.seed = (uint64_t)seed;
-  a.act_limit = (float)act_limit;
-  a.lo = (float)lo;
-  a.hi = (float)hi;
+  TORCH_CHECK(out_host.numel() == action.numel() && flag_host.numel() >= 1);
+  const ActArgs a = act_args(x, ws, bs, wmu, bmu, wls, bls, action, ctr,
+                             seed, act_limit, lo, hi);
   g_act_handles.push_back({a, ActPinned{out_host.data_ptr<float>(),
-                                        flag_host.data_ptr<int>()}});
+                                        flag_host.data_ptr<int>()},
+                           act_fast_fits(a), x.is_pinned()});
   return (int64_t)g_act_handles.size() - 1;
 }
 
 void act_fire(int64_t handle) {
   auto& h = g_act_handles.at((size_t)handle);
-  hipLaunchKernelGGL(act_kernel, dim3(1), dim3(256), 0, stream(),
-                     h.first, h.second);
+  act_launch(h.a, h.hp, h.fits);
+}
+
+bool act_handle_fast(int64_t handle) {
+  return g_act_handles.at((size_t)handle).fits && act_fast_mode_get();
+}
+
+// One native call per env step: observation in, launch, spin on the
+// completion flag, action out (act_sync.h).  False means the flag did not
+// land within actsync::kTimeoutS; nothing further has been launched and
+// the caller decides how to drain the stream.
+bool act_sync(int64_t handle, py::array obs, py::array out) {
+  auto& h = g_act_handles.at((size_t)handle);
+  TORCH_CHECK(h.x_pinned, "act_sync: the handle's observation buffer is "
+              "not pinned host memory");
+  auto f32vec = [](const py::array& v, int n) {
+    return py::isinstance<py::array_t<float>>(v) && v.ndim() == 1
+        && v.shape(0) == n && v.strides(0) == (py::ssize_t)sizeof(float);
+  };
+  TORCH_CHECK(f32vec(obs, h.a.O), "act_sync: obs must be a contiguous "
+              "float32 array of length ", h.a.O);
+  TORCH_CHECK(f32vec(out, h.a.A) && out.writeable(), "act_sync: out must "
+              "be a writeable contiguous float32 array of length ", h.a.A);
+  return actsync::run(const_cast<float*>(h.a.x),
+                       static_cast<const float*>(obs.data()), h.a.O,
+                       h.hp.out_host,
+                       static_cast<float*>(out.mutable_data()), h.a.A,
+                       h.hp.flag_host, actsync::kTimeoutS,
+                       [&] { act_launch(h.a, h.hp, h.fits); });
 }
 
 // Batched acting (evaluation path): rows [0, n) of x[*, O] (row stride
@@ -3911,6 +4269,18 @@ void register_fused(pybind11::module_& m) {
   m.def("act_step_pinned", &fused::act_step_pinned);
   m.def("act_prepare", &fused::act_prepare);
   m.def("act_fire", &fused::act_fire);
+  m.def("act_sync", &fused::act_sync,
+        "act_fire + host spin in one call: (handle, obs, out) -> landed");
+  m.def("act_fast_ok", &fused::act_fast_ok,
+        "host-only: do (obs_dim, trunk widths, act_dim) pass the shape "
+        "gate of the latency-shaped act kernel");
+  m.def("act_fast_mode", &fused::act_fast_mode,
+        "set TAC_AMD_ACT_FAST's mode (0 = act_kernel only), returns the "
+        "previous mode");
+  m.def("act_handle_fast", &fused::act_handle_fast,
+        "host-only: would act_fire(handle) launch the latency-shaped form");
+  m.def("act_last_fast", &fused::act_last_fast,
+        "host-only: did the last single-state act launch use it");
   m.def("act_batch", &fused::act_batch,
         "batched actor forward (deterministic or Philox-stochastic)");
 }
